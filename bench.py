@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- training-step throughput of the CGVAE hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload chignolin|dipeptide|protein2000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload chignolin|dipeptide|protein2000] [--full]
+                    [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one batch that is resident in HBM (coordinates + radius-graph neighbour
 lists, as ``CG_collate`` delivers them): the per-batch graph work the reference does inside ``model(batch)``
@@ -14,9 +15,11 @@ and a forward+backward-only figure are printed beside it.  Weak scaling: every r
 value = frames all ranks processed / max-over-ranks wall time.
 
 ``--gpus N`` without a torchrun environment starts the N ranks itself (one child process per GPU, before this process
-touches the GPU).  Rank 0 prints ONE JSON line with `parity` (one step with host-drawn noise against the CPU oracle),
-`roofline` (fused message-passing kernel, HIP events on the launch stream), `step_roofline`, `cpu_baseline`
-(the CPU oracle, a bounded sample, rank 0 / N=1 only).
+touches the GPU).  Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set up, warm up,
+time exactly ``--steps`` steps (one repetition), print.  ``--full`` adds everything else: ``--reps`` (default 5)
+repetitions of the timed loop, `parity` (one step with host-drawn noise against the CPU oracle), `roofline` (fused
+message-passing kernel, HIP events on the launch stream), the side figures, `cpu_baseline` (the CPU oracle, a bounded
+sample, rank 0 / N=1 only).  ``--dump-outputs DIR`` writes what the last timed step handed its caller as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -45,12 +48,19 @@ def parse():
     ap.add_argument("--n-basis", type=int, default=600)
     ap.add_argument("--frames-per-gpu", type=int, default=None)
     ap.add_argument("--rotation", type=int, default=8, help="number of different resident batches the timed loop cycles over")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the --steps loop (median and min are reported)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the --steps loop (median and min are reported); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: repetitions, parity against the CPU oracle, "
+                         "CPU baseline, per-kernel / roofline figures, side figures (each can be dropped by a --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss terms, model outputs, a fixed sample "
+                         "of the updated parameters) as DIR/<name>.npy")
     ap.add_argument("--skip-dead-vector-channel", action="store_true",
                     help="explicit option: do not compute the encoder's unused vector channel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline loop (profiling runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the side and per-kernel figures (profiling runs)")
     ap.add_argument("--cpu-steps", type=int, default=None)
     ap.add_argument("--optimizer", default="fused", choices=["fused", "torch"])
     ap.add_argument("--prefetch", action="store_true",
@@ -72,7 +82,10 @@ def parse():
                          "the next rung starts in a FRESH process (operands + graph -> gradients + graph -> gradients eager)")
     ap.add_argument("--no-supervisor", action="store_true",
                     help="multi-rank runs: measure in this process (no per-attempt timeout, no ladder) -- what a worker runs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    return args
 
 
 def visible_gpus() -> int:
@@ -472,6 +485,13 @@ def cpu_baseline(cg, workload: str, F: int, n_frames: int, steps: int):
                       f"({n_frames} frames, F={F}) after 1 warm-up, {dt * 1e3:.0f} ms/step, torch CPU {threads} threads"}
 
 
+def first_step_eps(batch, F):
+    """The host-drawn reparametrisation noise of a single-process run's first step (the parity check's; a plain run draws
+    the same, so that both take the same steps)."""
+    import torch
+    return torch.randn(batch["CG_nxyz"].shape[0], F, generator=torch.Generator().manual_seed(9))
+
+
 def parity_check(cg, model, trainer, batch, workload, F, frames):
     """One (untimed, eager) training step of the HIP path with host-drawn reparametrisation noise against the CPU
     oracle's forward + loss on the same batch, same initial weights, same noise (cgvae.py:486-513,
@@ -484,7 +504,7 @@ def parity_check(cg, model, trainer, batch, workload, F, frames):
     cpu_batch = {k: v.cpu() for k, v in batch.items() if torch.is_tensor(v)}
     hp = O.Hyper(F, w["n_rbf"], w["atom_cutoff"], w["cg_cutoff"], w["enc_nconv"], w["dec_nconv"], w["n_cgs"])
     P = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-    eps = torch.randn(cpu_batch["CG_nxyz"].shape[0], F, generator=torch.Generator().manual_seed(9))
+    eps = first_step_eps(cpu_batch, F)
     with torch.no_grad():
         out0 = O.model_forward(cpu_batch, P, hp, eps=eps)
         loss0, kl0, recon0, graph0 = O.loss_terms(out0, cpu_batch, w["beta"], w["gamma"])
@@ -522,6 +542,46 @@ def step_algorithmic_bytes(model, trainer, batch, F, R, w):
     edge = 2 * layers * (E * (16 + 4 * R) + 4 * N * 10 * F)
     return {"weights_fwd_bwd": 8 * n_live, "optimizer": 4 * (6 * n_rank + 8 * (n_live - n_rank)), "edge_kernels": edge,
             "total": 8 * n_live + 4 * (6 * n_rank + 8 * (n_live - n_rank)) + edge, "live_parameters": n_live}
+
+
+OUTPUT_NAMES = ("S_mu", "S_sigma", "H_prior_mu", "H_prior_sigma", "xyz", "xyz_recon")     # the model's forward, in order
+DUMP_MAX_ELEMENTS = 1 << 20         # per output array; larger ones are dumped as a fixed sample (4 MB each at fp32)
+DUMP_PARAM_SAMPLE = 2048            # elements per parameter tensor (all of a smaller one): < DUMP_MAX_ELEMENTS in all
+
+
+def _dump_sample(flat, k, seed):
+    """A fixed, seeded sample of ``k`` elements of the 1-D device tensor ``flat`` (all of it when it has at most ``k``)."""
+    import torch
+    n = flat.numel()
+    if n <= k:
+        return flat
+    idx = torch.randint(n, (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, trainer, model):
+    """``--dump-outputs``: what the last timed step handed its caller -- the loss and its terms, the model's forward
+    outputs and the updated parameters -- as ``path/<name>.npy`` (float32, or float64 where the tensor is).  The ~150 M
+    parameters are a fixed sample: DUMP_PARAM_SAMPLE elements of each tensor, drawn with a seed taken from its name
+    and concatenated in ``named_parameters`` order (``parameters_sample.npy``); in all well under 64 MB."""
+    import zlib
+    import numpy as np
+    import torch
+    trainer.flush()
+    torch.cuda.synchronize()
+    arrays = {"loss": trainer.last_loss}
+    arrays.update(zip(("kl", "recon", "graph"), trainer.last_terms))
+    arrays.update((n, t) for n, t in zip(OUTPUT_NAMES, trainer.last_out) if t is not None)
+    with torch.no_grad():
+        arrays["parameters_sample"] = torch.cat([_dump_sample(p.detach().reshape(-1), DUMP_PARAM_SAMPLE, zlib.crc32(n.encode()))
+                                                 for n, p in model.named_parameters()])
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            t = _dump_sample(t.reshape(-1), DUMP_MAX_ELEMENTS, zlib.crc32(name.encode()))
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
 
 
 def main():
@@ -603,14 +663,20 @@ def main():
 
     def first_steps(m, tr):
         nonlocal parity
-        # the very first step doubles as the parity check (rank 0 of a single-process run: weights still at their
-        # seeded initialisation, host-drawn noise, compared with the CPU oracle)
-        if not multi and not args.no_parity and parity is None:
+        # the very first step doubles as the parity check (--full, rank 0 of a single-process run: weights still at their
+        # seeded initialisation, host-drawn noise, compared with the CPU oracle); a plain run takes the same step unchecked
+        if not multi and args.full and not args.no_parity and parity is None:
             parity = parity_check(cg, m, tr, batch, args.workload, F, frames)
+        elif not multi and not args.full:
+            tr.step(batch, eps=first_step_eps(batch, F).to(dev))
         else:
             tr.step(batch)
-        # per-kernel HIP-event timing needs eager launches: done on a few untimed steps (part of warm-up)
+        # per-kernel HIP-event timing (--full) needs eager launches: done on a few untimed steps (part of warm-up)
         tr.step(batch)
+        if not args.full:
+            for _ in range(3):
+                tr.step(batch)
+            return {}
         with ktimer.KernelTimer(("equi_msg", "pseudo_msg")) as kt:
             for _ in range(3):
                 tr.step(batch)
@@ -675,6 +741,8 @@ def main():
     secs = timed_loop(step_clocked, args.steps, args.reps, barrier, dist, dev)
     trainer.flush()                                  # the update of the last timed step (the first one applied a pre-timed one)
     rot_replayed = trainer.replays - replays0
+    if args.dump_outputs and rank == 0:              # before any side measurement moves the parameters on
+        dump_outputs(args.dump_outputs, trainer, model)
     # what the data-parallel step moved, read NOW: the side measurements below capture other flavours of the step (a
     # forward+backward-only step exchanges nothing) and would leave their own bookkeeping behind
     dp_step, dp_info = "+allreduce", None
@@ -704,7 +772,7 @@ def main():
     value = world * frames * args.steps / med
     loss_end = float(trainer.last_loss)
 
-    extras_on = not args.no_extras
+    extras_on = args.full and not args.no_extras
     side = {}
     if extras_on:
         # the same step on ONE fixed batch (graph replay only: round 1's figure)
@@ -889,7 +957,7 @@ def main():
             step_bytes = {"bound": "hbm", "algorithmic_bytes": sb, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": gbs / HBM_PEAK_GBS}
         cpu = None
-        if not multi and not args.no_cpu_baseline:
+        if not multi and args.full and not args.no_cpu_baseline:
             steps_cpu = args.cpu_steps or (4 if args.workload == "chignolin" else 6)
             cpu = cpu_baseline(cg, args.workload, F, frames, steps_cpu)
         line = {

@@ -4,7 +4,7 @@
 w=$1; n=$2; shift 2
 for r in $(seq 1 $n); do
   for o in "$@"; do
-    python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-extras $o 2>/tmp/ab_err.txt | tail -1 > /tmp/ab_line.json
+    python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-extras $o 2>/tmp/ab_err.txt | tail -1 > /tmp/ab_line.json
     python - "$o" <<'PY'
 import json, sys
 try:

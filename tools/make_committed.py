@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """ONE script for everything bench.py reads back from profiles/: regenerates profiles/committed_kernel_times.json and
-profiles/pmc_traffic.json from a tools/collect_profiles.sh run (gpurun_out/<tag>_*), and stamps every entry with the
+profiles/pmc_traffic.json from a tools/collect_profiles.sh run (profile_out/<tag>_*), and stamps every entry with the
 sha256 of the kernel source file(s) it was measured on -- bench.py recomputes those hashes at run time and DROPS an entry
 whose kernel has changed since (there is no git on the GPU box: the file contents are the identity).
-    python tools/make_committed.py <tag>          (after copying gpurun_out/<tag>_* into profiles/)"""
+    python tools/make_committed.py <tag>          (reads profiles/<tag>_*, else profile_out/<tag>_*)"""
 import csv, hashlib, json, os, re, sys
 
 tag = sys.argv[1]
@@ -26,7 +26,7 @@ def source_hash(files):
 
 
 def src(path):
-    for d in ("profiles", "gpurun_out"):
+    for d in ("profiles", "profile_out"):
         p = os.path.join(root, d, path)
         if os.path.exists(p):
             return p
@@ -57,7 +57,7 @@ def pmc_means(path):
 
 times, traffic = {}, {"_comment": (
     "HBM-side traffic per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, eager launches of "
-    "`bench.py --no-graph`: the kernel runs between the other kernels of the step, caches as in training). FETCH_SIZE is in "
+    "`bench.py --full --no-graph`: the kernel runs between the other kernels of the step, caches as in training). FETCH_SIZE is in "
     "KiB and on gfx950 reports HALF the bytes of a coalesced read whatever the width per lane -- 4, 8 or 16 bytes -- and of "
     "8-byte row gathers too (tools/probes/fetch_calib.hip, profiles/%s_fetch_calibration.txt: 1 GiB streamed -> 524 29x KiB): "
     "every fetch figure is doubled. WRITE_SIZE is exact (1 GiB memset -> 1 048 576 KiB). Each entry carries the sha256 of the "
@@ -79,7 +79,7 @@ for w in ("chignolin", "dipeptide", "protein2000"):
             r = max(fwd, key=lambda r: int(r["TotalDurationNs"]))
             entry["message_forward"] = {
                 "kernel": r["Name"].split("(")[0].replace("void ", ""), "avg_us": float(r["AverageNs"]) / 1e3, "calls": int(r["Calls"]),
-                "source": f"profiles/{tag}_{w}_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `python bench.py --workload {w} --no-cpu-baseline --no-parity`)",
+                "source": f"profiles/{tag}_{w}_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `python bench.py --full --workload {w} --no-cpu-baseline --no-parity`)",
                 "source_sha256": source_hash(SOURCES["equi_msg_fwd"]), "source_files": SOURCES["equi_msg_fwd"]}
     seq = src(f"{tag}_step_sequence_{w}.txt")
     if seq:

@@ -1,11 +1,13 @@
 #!/bin/bash
-# usage: tools/step_sequence.sh [bench args]  -> gpurun_out/step_sequence.txt: ordered kernels of the last replayed step
+# usage: tools/step_sequence.sh [bench args]  -> $CGV_PROFILE_OUT/step_sequence.txt (default profile_out/): ordered kernels
+# of the last replayed step
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-rocprofv3 --kernel-trace --output-format csv -d /tmp/sq_$$ -o t -- python bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" > /tmp/sq_$$.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/sq_$$ -o t -- python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" > /tmp/sq_$$.log 2>&1
 tail -2 /tmp/sq_$$.log | cut -c1-200
-mkdir -p gpurun_out
-python - /tmp/sq_$$/t_kernel_trace.csv > gpurun_out/step_sequence.txt <<'PY'
+out=${CGV_PROFILE_OUT:-profile_out}
+mkdir -p "$out"
+python - /tmp/sq_$$/t_kernel_trace.csv > "$out"/step_sequence.txt <<'PY'
 import csv, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 # last step = after the last adam_update-but-one
@@ -26,4 +28,4 @@ for r in rows[lo:hi]:
     prev_end = e
 print(f"# {hi - lo} launches, span {(int(rows[hi-1]['End_Timestamp']) - t0) / 1e3:.1f} us")
 PY
-tail -1 gpurun_out/step_sequence.txt
+tail -1 "$out"/step_sequence.txt
