@@ -16,11 +16,11 @@
 // SplitN), and the block that draws the tile's last ticket adds the parts IN RANGE ORDER (not arrival order: repeated
 // launches are bit-identical) and runs the store epilogue once.
 //
-// Inside a block: 256 threads = 2 x 2 waves, each wave a 64 x 64 quarter of the tile as 4 x 4 v_mfma_f32_16x16x4_f32
+// Inside a block: 512 threads = 4 x 2 waves, each wave a 32 x 64 part of the tile as 2 x 4 v_mfma_f32_16x16x4_f32
 // accumulators (exact fp32 products, fp32 accumulation: the same arithmetic as the register-tile kernels).  A slab of A
 // ([128][32], rows padded to 36 floats) and of B (NT: [128][32] likewise; NN: [32][128], rows padded to 132) is staged
-// through registers: two register sets, so two slabs of global loads are in flight while a third is multiplied from LDS;
-// two LDS buffers, one barrier per slab (128 MFMAs per wave between barriers).  Fragments: 8 ds_read_b128 per 64 MFMAs.
+// through registers while the slab before it is multiplied from LDS; two LDS buffers, one barrier per slab (64 MFMAs per
+// wave between barriers).  Fragments: 12 ds_read_b128 per 64 MFMAs.
 //   NT: the product is formed transposed (B fragments as the MFMA's A operand) so that a lane ends with 4 consecutive n of
 //       one row m: bias, activation and stores are 16 bytes wide.
 //   NN: B fragments are float4s ALONG the output (W[r][n .. n + 3], r = the MFMA's reduction index); component s feeds

@@ -848,10 +848,11 @@ static thread_local SplitWs g_split_ws = {nullptr, 0, nullptr};
 constexpr size_t SPLIT_TICKET_BYTES = 64 * 1024;       // head of the workspace: one ticket per output tile
 
 /* Blocks per CU of the stream-K launch that should compute np problems of `rows` x `cols` outputs over a `red`-deep
- * reduction, or 0: the register-tile kernels.  CGV_OPT_STREAMK: 0 the measured rule, 1 never, 2 / 3 always (1 / 2 per CU). */
-static int sk_wanted(int rows, int cols, int red, int np, void* stream) {
+ * reduction, or 0: the register-tile kernels -- by shape and options alone (the launch also needs sk_ws_ready).
+ * CGV_OPT_STREAMK: 0 the measured rule, 1 never, 2 / 3 always (1 / 2 per CU). */
+static int sk_wanted(int rows, int cols, int red, int np) {
   const int opt = option(CGV_OPT_STREAMK);
-  if (opt == 1 || !g_split_ws.ws || g_split_ws.stream != stream) return 0;
+  if (opt == 1) return 0;
   if (opt == 2) return 1;
   if (opt == 3) return 2;
   if (opt >= 16) return -opt;                            /* experiments: a grid of exactly `opt` blocks */
@@ -863,6 +864,8 @@ static int sk_wanted(int rows, int cols, int red, int np, void* stream) {
   if (np != 1 || rows < 1536) return 0;
   return (cols <= 640 && red >= 1200) ? 1 : 0;
 }
+/* A workspace is registered for launches on `stream` (cgv_tile_bwd_input_split): stream-K and the split reduction may run. */
+static bool sk_ws_ready(void* stream) { return g_split_ws.ws && g_split_ws.stream == stream; }
 static bool sk_aligned(std::initializer_list<const void*> ptrs) {
   uintptr_t u = 0;
   for (const void* p : ptrs) u |= (uintptr_t)p;
@@ -877,15 +880,14 @@ int cgv_tile_supported(int M, int N, int K) {
          (int64_t)M * K < (1ll << 31) && (int64_t)N * K < (1ll << 31);
 }
 
-/* ``second`` != NULL: a pair launch (TileSecond).  Only the register-tile kernels take one; *pair_ok = 0 (nothing launched)
- * tells the caller that this shape runs on the LDS-staged kernels. */
+/* ``second`` != NULL: a pair launch (TileSecond).  The stream-K and register-tile kernels take both problems in one grid;
+ * the LDS-staged kernels take one, so a pair that lands on them runs as two launches inside this call. */
 static int tile_fwd_launch(const float* x, const float* W, const float* bias, float* y, float* z, int M, int N, int K, int act,
-                           void* stream, const cgv::TileSecond* second, int* pair_ok) {
+                           void* stream, const cgv::TileSecond* second) {
   hipStream_t st = (hipStream_t)stream;
   const cgv::TileSecond s2 = second ? *second : cgv::TileSecond{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   const unsigned np = second ? 2u : 1u;
-  if (pair_ok) *pair_ok = 1;
-  if (const int bpc = cgv::sk_wanted(M, N, K, (int)np, stream);
+  if (const int bpc = cgv::sk_ws_ready(stream) ? cgv::sk_wanted(M, N, K, (int)np) : 0;
       bpc != 0 && cgv::sk_aligned({x, W, bias, y, z, s2.x, s2.W, s2.bias, s2.y, s2.z})) {
     cgv::SkArgs a{};
     a.np = (int)np; a.M = M; a.N = N;
@@ -932,8 +934,8 @@ static int tile_fwd_launch(const float* x, const float* W, const float* bias, fl
                       (tiles64 >= lds_min && (M >= 1024 || lds_min <= 1) && aligned16 && !(lds_min >= 5 && lds_min <= 7)) ||
                       (lds_min >= 5 && lds_min <= 7);
   if (second && staged) {                       // the LDS-staged kernels take one problem: the pair as two launches of them
-    const int rc = tile_fwd_launch(x, W, bias, y, z, M, N, K, act, stream, nullptr, nullptr);
-    return rc ? rc : tile_fwd_launch(s2.x, s2.W, s2.bias, s2.y, s2.z, M, N, K, s2.act, stream, nullptr, nullptr);
+    const int rc = tile_fwd_launch(x, W, bias, y, z, M, N, K, act, stream, nullptr);
+    return rc ? rc : tile_fwd_launch(s2.x, s2.W, s2.bias, s2.y, s2.z, M, N, K, s2.act, stream, nullptr);
   }
   if (ring_ok && (tiles64 >= lds_min || lds_min == 3)) {
     const dim3 grid((N + 63) / 64, (M + 63) / 64);
@@ -963,12 +965,11 @@ int cgv_tile_linear_fwd(const float* x, const float* W, const float* bias, float
   CGV_REQUIRE(act >= 0 && act <= cgv::CGV_ACT_MAX, "act must be 0 (identity), 1 (swish), 2 (tanh), 3 (relu), 4 / 5 (c + exp(z/2))");
   CGV_REQUIRE(cgv_tile_supported(M, N, K), "unsupported shape (need N % 4 == 0, K % 4 == 0)");
   CGV_REQUIRE(((((uintptr_t)x | (uintptr_t)W)) & 15) == 0, "x and W must be 16-byte aligned");
-  return tile_fwd_launch(x, W, bias, y, z, M, N, K, act, stream, nullptr, nullptr);
+  return tile_fwd_launch(x, W, bias, y, z, M, N, K, act, stream, nullptr);
 }
 
-/* Two layers of ONE shape in one launch: y_a = act(x_a W_a^T + b_a), y_b = act(x_b W_b^T + b_b) (x_a may equal x_b).
- * Returns CGV_E_UNSUPPORTED-style non-zero with nothing launched when the shape runs on the LDS-staged kernels
- * (cgv_tile_pair_supported tells beforehand). */
+/* Two layers of ONE shape in one call: y_a = act(x_a W_a^T + b_a), y_b = act(x_b W_b^T + b_b) (x_a may equal x_b) -- one
+ * launch, or two where the shape runs on the LDS-staged kernels (tile_fwd_launch). */
 int cgv_tile_pair_supported(int M, int N, int K) {
   /* every tile-supported shape: the stream-K kernel and the register-tile kernels take the second problem in the same
    * launch, the LDS-staged single-problem kernels run the pair as two launches inside the one call */
@@ -987,10 +988,7 @@ int cgv_tile_pair_linear_fwd(const float* x_a, const float* W_a, const float* bi
   CGV_REQUIRE(((((uintptr_t)x_a | (uintptr_t)W_a | (uintptr_t)x_b | (uintptr_t)W_b | (uintptr_t)y_a | (uintptr_t)y_b |
                  (uintptr_t)z_a | (uintptr_t)z_b | (uintptr_t)bias_a | (uintptr_t)bias_b)) & 15) == 0, "operands must be 16-byte aligned");
   const cgv::TileSecond s2{x_b, W_b, bias_b, y_b, z_b, act_b};
-  int ok = 1;
-  const int rc = tile_fwd_launch(x_a, W_a, bias_a, y_a, z_a, M, N, K, act, stream, &s2, &ok);
-  if (!ok) { cgv::set_error("cgv_tile_pair_linear_fwd: this shape runs on the LDS-staged kernels (no pair launch)"); return CGV_E_UNSUPPORTED; }
-  return rc;
+  return tile_fwd_launch(x_a, W_a, bias_a, y_a, z_a, M, N, K, act, stream, &s2);
 }
 
 
@@ -1005,6 +1003,42 @@ static int split_shares(int tiles, int N) {
   return n < 1 ? 1 : n;
 }
 
+namespace cgv {
+enum BwdKernel { BWD_R16_W8, BWD_R16_W16, BWD_R32_W8, BWD_R32_W4 };      // tile_bwd_input_k<row tiles of 16, waves>
+struct BwdInputChoice {
+  int bpc;            // stream-K blocks per CU (0: none) -- taken when the call's own operands allow it, else `kernel`
+  BwdKernel kernel;   // the register-tile kernel
+  int shares;         // blocks per output tile of its split reduction (BWD_R16_W16 with a workspace; else 1)
+};
+
+/* The kernel a backward-input launch of np problems [M, N] x [N, K] takes by shape, options and whether a workspace is
+ * registered for its stream -- ONE rule for tile_bwd_input_launch and cgv_tile_bwd_input_plan. */
+static BwdInputChoice bwd_input_choice(int M, int N, int K, int np, bool ws) {
+  BwdInputChoice c{ws ? sk_wanted(M, K, N, np) : 0, BWD_R16_W8, 1};
+  const int kt = (K + 63) / 64;
+  const int blocks32 = kt * ((M + 31) / 32);
+  const int blocks16 = kt * ((M + 15) / 16);
+  const int ow = option(CGV_OPT_BWD_INPUT_WAVES);
+  int waves = 8;
+  if (ow > 0 && ow != 32) waves = ow;                   // experiments only
+  else if (blocks16 < 128 && N >= 1024) waves = 16;
+  if (ow == 32 || (blocks32 >= 200 && blocks32 < 512 && waves == 8))
+    // (ow == 32: A/B.)  200 .. 511 32-row tiles (704 rows x 600 / 1200 columns): still 32-row tiles, with the reduction split
+    // over 8 waves -- half the weight re-reads of the 16-row tiles (704 x 1800 x 600: 22.9 against 25.0 us, 704 x 5400:
+    // 54.6 / 64.1; at 332 rows the 16-row tiles win, 14.5 against 22.1 us: tools/gemm_shapes.py)
+    c.kernel = BWD_R32_W8;
+  else if (blocks32 >= 512)               // enough 32-row tiles to fill the chip: halve the weight re-reads
+    c.kernel = BWD_R32_W4;
+  else if (waves == 16) {                 // few output tiles and a long reduction (96 bead rows x 5400 columns: 60 blocks):
+    // 16 waves per block split it -- 60 blocks of 8 waves left three quarters of the chip idle (17.8 us per call) -- and,
+    // with a registered workspace, 2 - 4 blocks per tile split it further (SplitN)
+    c.kernel = BWD_R16_W16;
+    if (ws) c.shares = split_shares(blocks16 * np, N);
+  }
+  return c;
+}
+}  // namespace cgv
+
 static int tile_bwd_input_launch(const float* g, const float* z, int act, const float* W, float* gx, int M, int N, int K,
                                  void* stream, const char* what, const float* add = nullptr,
                                  cgv::BcastAdd bc = cgv::BcastAdd{nullptr, nullptr, nullptr, 0},
@@ -1015,8 +1049,9 @@ static int tile_bwd_input_launch(const float* g, const float* z, int act, const 
   hipStream_t st = (hipStream_t)stream;
   const cgv::BwdSecond s2 = second ? *second : cgv::BwdSecond{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
   const unsigned np = second ? 2u : 1u;
+  const cgv::BwdInputChoice choice = cgv::bwd_input_choice(M, N, K, (int)np, cgv::sk_ws_ready(stream));
   // no activation in the operand loads (act_downstream chains carry none), operands 16-byte aligned: the stream-K kernel
-  if (const int bpc = cgv::sk_wanted(M, K, N, (int)np, stream);
+  if (const int bpc = choice.bpc;
       bpc != 0 && !ns.stack && act == 0 && (!more.g || more.act == 0) && (!second || s2.act == 0) &&
       cgv::sk_aligned({g, W, gx, add, bc.src, more.g, more.W, oa.z, oa.z2, s2.g, s2.W, s2.gx, s2.add})) {
     cgv::SkArgs a{};
@@ -1034,60 +1069,47 @@ static int tile_bwd_input_launch(const float* g, const float* z, int act, const 
       return cgv::check_launch(what);
   }
   const int kt = (K + 63) / 64;
-  const int blocks32 = kt * ((M + 31) / 32);
-  const int blocks16 = kt * ((M + 15) / 16);
-  int waves = 8;
-  if (const int o = cgv::option(CGV_OPT_BWD_INPUT_WAVES); o > 0 && o != 32) waves = o;          // experiments only
-  else if (blocks16 < 128 && N >= 1024) waves = 16;
-  if (cgv::option(CGV_OPT_BWD_INPUT_WAVES) == 32)          /* A/B: 32-row tiles, 8 waves */
-    hipLaunchKernelGGL((cgv::tile_bwd_input_k<2, 8>), dim3(kt, (M + 31) / 32, np), dim3(512), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
-  else if (blocks32 >= 200 && blocks32 < 512 && waves == 8)
-    // 200 .. 511 32-row tiles (704 rows x 600 / 1200 columns): still 32-row tiles, with the reduction split over 8 waves --
-    // half the weight re-reads of the 16-row tiles (704 x 1800 x 600: 22.9 against 25.0 us, 704 x 5400: 54.6 / 64.1;
-    // at 332 rows the 16-row tiles win, 14.5 against 22.1 us: tools/gemm_shapes.py)
-    hipLaunchKernelGGL((cgv::tile_bwd_input_k<2, 8>), dim3(kt, (M + 31) / 32, np), dim3(512), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
-  else if (blocks32 >= 512)               // enough 32-row tiles to fill the chip: halve the weight re-reads
-    hipLaunchKernelGGL((cgv::tile_bwd_input_k<2, 4>), dim3(kt, (M + 31) / 32, np), dim3(256), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
-  else if (waves == 16) {                 // few output tiles and a long reduction (96 bead rows x 5400 columns: 60 blocks):
-    // 16 waves per block split it -- 60 blocks of 8 waves left three quarters of the chip idle (17.8 us per call) -- and,
-    // with a registered workspace, 2 - 4 blocks per tile split it further (SplitN)
-    cgv::SplitN sp{nullptr, nullptr, 1};
-    const int tiles = blocks16 * (int)np;
-    const cgv::SplitWs& w = cgv::g_split_ws;
-    if (w.ws && w.stream == stream) {
-      const int n = split_shares(tiles, N);
-      const size_t need = cgv::SPLIT_TICKET_BYTES + (size_t)tiles * n * (16 * 64) * sizeof(float);
-      if (n > 1 && need <= w.bytes && (size_t)tiles * sizeof(unsigned) <= cgv::SPLIT_TICKET_BYTES) {
+  switch (choice.kernel) {
+    case cgv::BWD_R32_W8:
+      hipLaunchKernelGGL((cgv::tile_bwd_input_k<2, 8>), dim3(kt, (M + 31) / 32, np), dim3(512), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
+      break;
+    case cgv::BWD_R32_W4:
+      hipLaunchKernelGGL((cgv::tile_bwd_input_k<2, 4>), dim3(kt, (M + 31) / 32, np), dim3(256), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
+      break;
+    case cgv::BWD_R16_W16: {
+      cgv::SplitN sp{nullptr, nullptr, 1};
+      const int tiles = kt * ((M + 15) / 16) * (int)np;
+      const cgv::SplitWs& w = cgv::g_split_ws;
+      const size_t need = cgv::SPLIT_TICKET_BYTES + (size_t)tiles * choice.shares * (16 * 64) * sizeof(float);
+      if (choice.shares > 1 && need <= w.bytes && (size_t)tiles * sizeof(unsigned) <= cgv::SPLIT_TICKET_BYTES) {
         sp.ticket = reinterpret_cast<unsigned*>(w.ws);
         sp.part = reinterpret_cast<float*>(reinterpret_cast<char*>(w.ws) + cgv::SPLIT_TICKET_BYTES);
-        sp.n = n;
+        sp.n = choice.shares;
       }
+      hipLaunchKernelGGL((cgv::tile_bwd_input_k<1, 16>), dim3(kt, ((M + 15) / 16) * sp.n, np), dim3(1024), 0, st, g, W, gx, M, N, K, z, act,
+                         add, bc, s2, more, oa, sp, ns);
+      break;
     }
-    hipLaunchKernelGGL((cgv::tile_bwd_input_k<1, 16>), dim3(kt, ((M + 15) / 16) * sp.n, np), dim3(1024), 0, st, g, W, gx, M, N, K, z, act,
-                       add, bc, s2, more, oa, sp, ns);
+    case cgv::BWD_R16_W8:
+      hipLaunchKernelGGL((cgv::tile_bwd_input_k<1, 8>), dim3(kt, (M + 15) / 16, np), dim3(512), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
+      break;
   }
-  else
-    hipLaunchKernelGGL((cgv::tile_bwd_input_k<1, 8>), dim3(kt, (M + 15) / 16, np), dim3(512), 0, st, g, W, gx, M, N, K, z, act, add, bc, s2, more, oa, cgv::SplitN{nullptr, nullptr, 1}, ns);
   return cgv::check_launch(what);
 }
 
-/* What a backward-input launch of this shape does with a registered workspace: *shares = blocks per output tile of the
- * split reduction (1: unsplit), *streamk = 1 when the stream-K kernel takes it (np = 1 single launch, 2 pair launch).
- * The dispatch rules of tile_bwd_input_launch, for callers that choose between this entry point and the row-split kernel
- * (primitives._LinearFn, ops._dense_bwd_input): the workspace is per (host thread, stream) state the call itself cannot see. */
+/* What a backward-input launch of this shape does with a registered workspace (cgv::bwd_input_choice): *shares = blocks per
+ * output tile of the split reduction (1: unsplit), *streamk = 1 when the stream-K kernel is wanted (np = 1 single launch,
+ * 2 pair launch).  For callers that choose between this entry point and the row-split kernel (primitives.bwd_input_choice):
+ * the workspace is per (host thread, stream) state the call itself cannot see.  The plan does not see the conditions that
+ * depend on the call's own arguments either: an activation in the operand loads (act != 0), operands that are not 16-byte
+ * aligned and the norm / stack epilogue (ns.stack) keep a launch off the stream-K kernel; it then runs on the register tiles,
+ * whose split the plan does not report beside *streamk = 1 (*shares = 1 there). */
 int cgv_tile_bwd_input_plan(int M, int N, int K, int np, int* shares, int* streamk) {
   CGV_REQUIRE(shares && streamk && np >= 1 && np <= 2, "bad argument");
   CGV_REQUIRE(cgv_tile_supported(M, N, K), "unsupported shape (need N % 4 == 0, K % 4 == 0)");
-  *shares = 1;
-  const int opt_sk = cgv::option(CGV_OPT_STREAMK);
-  *streamk = (opt_sk == 2 || opt_sk == 3 || opt_sk >= 16) ? 1 : (opt_sk == 1 ? 0 : (np == 1 && M >= 1536 && K <= 640 && N >= 1200));
-  if (*streamk) return 0;
-  const int kt = (K + 63) / 64, blocks16 = kt * ((M + 15) / 16);
-  const int ow = cgv::option(CGV_OPT_BWD_INPUT_WAVES);
-  const bool waves16 = (ow > 0 && ow != 32) ? ow == 16 : (blocks16 < 128 && N >= 1024);
-  const int blocks32 = kt * ((M + 31) / 32);
-  if (ow == 32 || (blocks32 >= 200 && !waves16) || !waves16) return 0;      // (the 8-wave / 32-row kernels never split)
-  *shares = split_shares(blocks16 * np, N);
+  const cgv::BwdInputChoice c = cgv::bwd_input_choice(M, N, K, np, true);
+  *streamk = c.bpc != 0;
+  *shares = c.bpc != 0 ? 1 : c.shares;
   return 0;
 }
 

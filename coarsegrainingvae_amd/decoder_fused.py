@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .ktimer import mark
-from .primitives import ACT_NONE, ACT_SWISH, Swish, _grad_target, _is_direct, wgrad_queue
+from .primitives import ACT_NONE, ACT_SWISH, Swish, _grad_target, _is_direct, wgrad_queue, wgrad_sink
 
 _F32 = torch.float32
 PER_LAYER = 12          # W1 b1 W2 b2 Wd bd Wu Wv W0 b0 W1p b1p
@@ -198,27 +198,13 @@ class _PseudoDecoderFn(torch.autograd.Function):
             _lib.call("cgv_decoder_dense_bwd", _lib.ptr(p4), nb, fl16(F), _lib.ptr(z1), ACT_SWISH, _lib.ptr(pW1.detach()),
                       _lib.ptr(g_a1), _lib.ptr(p5), fl16(F), n, F, F, st)
 
-            # ---- weight gradients -> the grouped launch (direct arena targets)
-            def enqueue(gy, x, z, act, pw, pb):
-                tw, acc_w, _ = _grad_target(pw, pw)
-                tb, acc_b, _ = _grad_target(pb, pb)
-                if acc_b != acc_w:
-                    raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-                wgrad_queue.enqueue(gy, x, z, act, tw, tb, acc_w)
-            enqueue(ga, a0, None, ACT_NONE, pW1p, pb1p)
-            enqueue(g_a0, stack, z0, ACT_SWISH, pW0, pb0)
-            tu, acc_u, _ = _grad_target(pWu, pWu)
-            tv, acc_v, _ = _grad_target(pWv, pWv)
-            if acc_u != acc_v:
-                raise RuntimeError("u_mat / v_mat disagree on first-write / accumulate state")
-            wgrad_queue.enqueue(gUV, rows, None, ACT_NONE, torch.as_strided(tu, (2 * F, F), (F, 1)), None, acc_u)
-            enqueue(g_phi, a1, None, ACT_NONE, pW2, pb2)
-            enqueue(g_a1, S_in, z1, ACT_SWISH, pW1, pb1)
-            pWu._cgv_rank = pWv._cgv_rank = (3 * n, 2 * F, F)
-            pW1p._cgv_rank, pW0._cgv_rank = (n, 3 * F, F), (n, F, 2 * F)
-            for pw, pb, shape in ((pW2, pb2, (n, 9 * F, F)), (pW1, pb1, (n, F, F))):
-                pw._cgv_exch = pw._cgv_rank = shape
-                pb._cgv_exch = shape
+            # ---- weight gradients -> the grouped launch (direct arena targets); the UpdateBlock's weights are tagged with
+            # their operand rows only (no ``_cgv_exch``, as ops._UpdateBlockFused)
+            wgrad_sink(pW1p, pb1p, ga, a0, None, ACT_NONE, (n, 3 * F, F), exch=False, flush=False)
+            wgrad_sink(pW0, pb0, g_a0, stack, z0, ACT_SWISH, (n, F, 2 * F), exch=False, flush=False)
+            wgrad_sink(pWu, None, gUV, rows, None, ACT_NONE, (3 * n, 2 * F, F), exch=False, stacked=pWv, flush=False)
+            wgrad_sink(pW2, pb2, g_phi, a1, None, ACT_NONE, (n, 9 * F, F), flush=False)
+            wgrad_sink(pW1, pb1, g_a1, S_in, z1, ACT_SWISH, (n, F, F), flush=False)
             # ---- gradients of this layer's inputs = of the layer below's outputs
             gS = Slices(g_s, p5, nF, fl16(F))
             gV, gSbar, gVbar = g_v, g_sbar, g_vbar

@@ -10,12 +10,13 @@ from __future__ import annotations
 from typing import Optional
 
 import ctypes as C
+from types import SimpleNamespace
 
 import torch
 
 from . import _lib, options
 from .graph import EdgeGeometry, EdgePlan
-from .primitives import linear as _linear, skinny_bwd_input
+from .primitives import FWD_ENTRY, bwd_input_choice, bwd_input_launch, fwd_choice, linear as _linear, wgrad_queue, wgrad_sink
 
 _F32 = torch.float32
 
@@ -161,7 +162,6 @@ class _EquiMessage(torch.autograd.Function):
         lib = _lib.load()
         ws_bytes = int(lib.cgv_equi_msg_bwd_workspace_bytes(plan.n_src, F, geom.n_rbf))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        from .primitives import wgrad_queue
         if wgrad_queue.active and ret_W is None and ret_b is None:
             # under the trainer: the filter gradients feed the optimiser only -- their reduction joins those of the
             # step's other message blocks in one launch when the queue is flushed (primitives.flush_filters)
@@ -581,7 +581,6 @@ class _PseudoMessage(torch.autograd.Function):
         lib = _lib.load()
         ws_bytes = int(lib.cgv_pseudo_msg_bwd_workspace_bytes(n, F, geom.n_rbf))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=s.device)
-        from .primitives import wgrad_queue
         if wgrad_queue.active and ret_W is None and ret_b is None:
             # under the trainer: the reduction of the filter-gradient partial sums joins the step's other message blocks in
             # one launch when the queue is flushed (one link less in every decoder layer's backward chain)
@@ -690,37 +689,27 @@ def _adjacent(first, second):
 
 
 def _dense_fwd(x, W, b, y, z, M, N, K, act, st):
-    """z = x W^T + b, y = act(z) on the kernel the Dense layers would pick for this shape (primitives._gemm_mode)."""
-    lib = _lib.load()
-    # up to 64 rows the weight-streaming kernel; 65 - 128 rows and at most 1200 outputs it still beats the tiles (96 rows:
-    # 600 x 1200 6.3 against 10.5 - 13 us -- the rule of primitives._LinearFn.forward, which the fused UpdateBlock missed)
-    few_rows = M <= 128 and N <= 1200 and lib.cgv_skinny_fwd_supported(M, N, K) and (b is None or b.data_ptr() % 16 == 0)
-    name = "cgv_skinny_linear_fwd" if (lib.cgv_skinny_supported(M, N, K) or few_rows) else "cgv_tile_linear_fwd"
-    _lib.call(name, _lib.ptr(x) if torch.is_tensor(x) else x, _lib.ptr(W), _lib.ptr(b), _lib.ptr(y) if torch.is_tensor(y) else y,
-              _lib.ptr(z), M, N, K, act, st)
+    """z = x W^T + b, y = act(z) on the kernel the Dense layers would pick for this shape (primitives.fwd_choice).  The
+    block's biases sit in the trainer's arena (256-byte aligned)."""
+    # (up to 16 rows the skinny kernel, not the decoder's 4-column one, and 33 - 64 rows x >= 4096 outputs stay on it too:
+    # the fused block's products were measured on the skinny kernel only)
+    kind = fwd_choice(M, N, K, b is None or b.data_ptr() % 16 == 0, decoder_dense=False, wide_tiles=False)
+    _lib.call(FWD_ENTRY[kind], _lib.ptr(x) if torch.is_tensor(x) else x, _lib.ptr(W), _lib.ptr(b),
+              _lib.ptr(y) if torch.is_tensor(y) else y, _lib.ptr(z), M, N, K, act, st)
 
 
-def _dense_bwd_input(gy, z, W, gx, M, N, K, act, st, z_out=None, act_out=0) -> bool:
-    """gx = (gy * act'(z)) W: row-split kernel up to 64 rows (and for few rows x very long reductions), tile kernel above.
-    ``z_out`` [M, K]: the pre-activation of the layer that produced this layer's input -- the tile kernel then stores
-    gx * act_out'(z_out) (returns True: the producing layer's backward runs without an activation); the row-split kernel has
-    no such epilogue (returns False, gx as it is)."""
-    lib = _lib.load()
-    # (33 - 64 rows below 4096 columns: the tile kernel, whose reduction splits over 2-4 blocks per tile, beats the row-split
-    # kernel + its reduction launch: 8.0 - 8.7 against 11.7 - 12.0 us at 64 x 1200 / 1800, primitives._LinearFn)
-    tile_wins = 32 < M <= 64 and N < 4096 and _lib.split_workspace_ready() and lib.cgv_tile_supported(M, N, K) \
-        and gy.data_ptr() % 16 == 0
-    if (lib.cgv_skinny_supported(M, N, K) and not tile_wins) or (M <= 128 and N >= 4096 and lib.cgv_skinny_bwd_input_supported(M, N, K)
-                                                                 and not (M > 64 and _lib.split_workspace_ready())):
-        skinny_bwd_input(gy, z, W, gx, M, N, K, act, st)
-        return False
-    if z_out is not None and act_out and options.HOST["act_downstream"]:
-        _lib.call("cgv_tile_linear_bwd_input_out", _lib.ptr(gy), _lib.ptr(z) if act else None, _lib.ptr(W), None, _lib.ptr(gx),
-                  M, N, K, act, _lib.ptr(z_out), int(act_out), st)
-        return True
-    _lib.call("cgv_tile_linear_bwd_input_act", _lib.ptr(gy), _lib.ptr(z) if act else None, _lib.ptr(W), _lib.ptr(gx),
-              M, N, K, act, st)
-    return False
+def _dense_bwd_input(gy, z, W, gx, M, N, K, act, z_out=None, act_out=0) -> bool:
+    """gx = (gy * act'(z)) W on the kernel of primitives.bwd_input_choice.  ``z_out`` [M, K]: the pre-activation of the layer
+    that produced this layer's input -- the tile kernel then stores gx * act_out'(z_out) (returns True: the producing layer's
+    backward runs without an activation); on the row-split kernel it is not applied here (returns False, gx as it is)."""
+    # (33 - 64 rows at most 1024 columns take the tile kernel only where it may split its reduction: without a split
+    # workspace, in a capture, the fused block keeps the row split it was measured with)
+    kind = bwd_input_choice(M, N, K, _lib.split_workspace_ready(), gy_aligned=gy.data_ptr() % 16 == 0, short_tiles=False)
+    prod = None
+    if kind == "tile" and z_out is not None and act_out and options.HOST["act_downstream"]:
+        prod = SimpleNamespace(saved_tensors=(None, None, z_out), act=act_out, act_done=False)    # the producing layer
+    bwd_input_launch(kind, gy, z, act, W, gx, producer=prod)
+    return prod is not None and prod.act_done
 
 
 class _UpdateBlockFused(torch.autograd.Function):
@@ -790,7 +779,6 @@ class _UpdateBlockFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_ds, g_dv):
-        from .primitives import _grad_target, wgrad_queue
         if g_ds is None and g_dv is None:
             return (None,) * 9
         vt, UV, stack, z0, a0, a, W0d, W1d = ctx.saved_tensors
@@ -806,7 +794,7 @@ class _UpdateBlockFused(torch.autograd.Function):
                   _lib.ptr(ga), n, F, 2 * F, st)
         g_a0, g_stack, g_s, g_vt, g_v = new(n, F), new(n, 2 * F), new(n, F), new(3 * n, F), new(n, F, 3)
         # (tile kernels: the second layer's product leaves g_a0 * Swish'(z0), the first layer's launches run without an activation)
-        act0 = 0 if _dense_bwd_input(ga, None, W1d, g_a0, n, 3 * F, F, 0, st, z0, 1) else 1
+        act0 = 0 if _dense_bwd_input(ga, None, W1d, g_a0, n, 3 * F, F, 0, z0, 1) else 1
         lib = _lib.load()
         if (options.HOST["update_fused_bwd"] and n > 32 and lib.cgv_tile_supported(n, F, 2 * F) and F % 4 == 0
                 and (n > 64 or _lib.split_workspace_ready()) and all(t.data_ptr() % 16 == 0 for t in (g_a0, W0d, stack, UV, gUV, g_s))
@@ -815,30 +803,18 @@ class _UpdateBlockFused(torch.autograd.Function):
             _lib.call("cgv_tile_linear_bwd_input_norm_stack", _lib.ptr(g_a0), _lib.ptr(z0) if act0 else None, _lib.ptr(W0d), n, F, 2 * F,
                       act0, _lib.ptr(stack), Vv_ptr, _lib.ptr(g_ds) if ctx.residual else None, _lib.ptr(g_s), gVv_ptr, 2 * F, 1, st)
         else:
-            _dense_bwd_input(g_a0, z0 if act0 else None, W0d, g_stack, n, F, 2 * F, act0, st)
+            _dense_bwd_input(g_a0, z0 if act0 else None, W0d, g_stack, n, F, 2 * F, act0)
             _lib.call("cgv_update_norm_stack_bwd", _lib.ptr(g_stack), Vv_ptr, _lib.ptr(stack),
                       _lib.ptr(g_ds) if ctx.residual else None, _lib.ptr(g_s), gVv_ptr, n, F, 2 * F, 1, st)
         Wuv = torch.as_strided(u_w.detach(), (2 * F, F), (F, 1))
-        _dense_bwd_input(gUV, None, Wuv, g_vt, 3 * n, 2 * F, F, 0, st)
+        _dense_bwd_input(gUV, None, Wuv, g_vt, 3 * n, 2 * F, F, 0)
         _lib.call("cgv_update_vec_from_rows", _lib.ptr(g_vt), _lib.ptr(g_dv) if ctx.residual else None, _lib.ptr(g_v),
                   n, F, st)
-        # weight gradients -> grouped launch (direct targets; the [u_mat; v_mat] pair is one problem)
-        tu, acc_u, _ = _grad_target(u_w, u_w)
-        tv, acc_v, _ = _grad_target(v_w, v_w)
-        if acc_u != acc_v:
-            raise RuntimeError("u_mat / v_mat disagree on first-write / accumulate state")
-        wgrad_queue.enqueue(gUV, vt, None, 0, torch.as_strided(tu, (2 * F, F), (F, 1)), None, acc_u)
-        t1, acc1, _ = _grad_target(W1, W1)
-        tb1, accb1, _ = _grad_target(b1, b1)
-        wgrad_queue.enqueue(ga, a0, None, 0, t1, tb1, acc1)
-        t0, acc0, _ = _grad_target(W0, W0)
-        tb0, accb0, _ = _grad_target(b0, b0)
-        wgrad_queue.enqueue(g_a0, stack, z0 if act0 else None, act0, t0, tb0, acc0)
-        # operand rows of these weights' gradient problems (trainer: rank-update layers go to the front of the arena)
-        u_w._cgv_rank = v_w._cgv_rank = (3 * n, 2 * F, F)
-        W1._cgv_rank, W0._cgv_rank = (n, W1.shape[0], W1.shape[1]), (n, W0.shape[0], W0.shape[1])
-        if acc1 != accb1 or acc0 != accb0:
-            raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
+        # weight gradients -> grouped launch (direct targets; the [u_mat; v_mat] pair is one problem).  Tagged with their
+        # operand rows only (``_cgv_rank``, no ``_cgv_exch``): these layers take no part in the operand exchange
+        wgrad_sink(u_w, None, gUV, vt, None, 0, (3 * n, 2 * F, F), exch=False, stacked=v_w, flush=False)
+        wgrad_sink(W1, b1, ga, a0, None, 0, (n, W1.shape[0], W1.shape[1]), exch=False, flush=False)
+        wgrad_sink(W0, b0, g_a0, stack, z0, act0, (n, W0.shape[0], W0.shape[1]), exch=False, flush=False)
         if not wgrad_queue.active:
             wgrad_queue.flush()
         return g_s, g_v, None, None, None, None, None, None, None

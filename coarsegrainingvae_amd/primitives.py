@@ -439,7 +439,8 @@ class _LinearFn(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1])
         ctx.params = (weight, bias)
         ctx.act = act
-        ctx.mode = mode = _gemm_mode(x2, weight, bias)
+        ctx.mode = _gemm_mode(x2, weight, bias)            # the kernel family: "skinny" (<= 64 rows) or "tile"
+        ctx.bias_aligned = bias is None or bias.data_ptr() % 16 == 0
         N = weight.shape[0]
         x2 = x2.contiguous()
         if x2.data_ptr() % 16:
@@ -447,33 +448,16 @@ class _LinearFn(torch.autograd.Function):
         M, K = x2.shape
         y = torch.empty(M, N, dtype=torch.float32, device=x.device)
         z = torch.empty_like(y) if act else None
-        if mode == "skinny" and M <= 16 and N >= 64:
-            # few rows: 4-column blocks (N / 4 of them pull the weight) beat the skinny kernel's 16-column blocks
-            # (decoder forward 356 -> 343 us on chignolin: csrc/decoder_layer.hip, dec_dense_fwd_k)
-            _lib.call("cgv_decoder_dense_fwd", _lib.ptr(x2), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), _lib.ptr(z),
-                      M, N, K, act, _lib.stream_ptr())
-        else:
-            # 65 - 128 rows (a big bead batch) and at most 1200 outputs: the weight-streaming kernel with one 16-row block
-            # per thread block still beats the tiles (96 rows: 600 x 600 4.8 against 6.7 us, 600 x 1200 6.3 / 10.5,
-            # 1200 x 600 5.9 / 6.7; from 1800 outputs on the tiles win: tools/fwd_bench.py)
-            few_rows = mode == "tile" and M <= 128 and N <= 1200 and (bias is None or bias.data_ptr() % 16 == 0)
-            # 33 - 64 rows and a very wide layer (64 beads x 5400 outputs): the tiles win (11.7 against 14.2 us)
-            wide = mode == "skinny" and M > 32 and N >= 4096 and lib_tile_ok(M, N, K)
-            _lib.call("cgv_skinny_linear_fwd" if ((mode == "skinny" and not wide) or few_rows) else "cgv_tile_linear_fwd", _lib.ptr(x2),
-                      _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), _lib.ptr(z), M, N, K, act, _lib.stream_ptr())
+        _lib.call(FWD_ENTRY[fwd_choice(M, N, K, ctx.bias_aligned)], _lib.ptr(x2), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y),
+                  _lib.ptr(z), M, N, K, act, _lib.stream_ptr())
         ctx.save_for_backward(x2, weight, z)
         return y.reshape(x.shape[:-1] + (N,))
 
     @staticmethod
     def backward(ctx, gy, g_alias=None):
         if gy is None:                                       # only the forked alias was used downstream
-            # the layer's output left the loss: its weight / bias gradient is zero.  Arena-managed (direct-write)
-            # parameters get no zero fill at the start of a step (ParamArena.zero_grad only flags them pending), so the
-            # zero has to be written here -- otherwise last step's gradient would enter the norm, the clip and the update
-            for prm in ctx.params:
-                if _is_direct(prm) and prm._cgv_pending and ctx.needs_input_grad[1]:
-                    prm.grad.zero_()
-                    prm._cgv_pending = False
+            if ctx.needs_input_grad[1]:
+                zero_unreached(ctx.params)
             return _LinearFn._with_parked(ctx, g_alias), None, None, None, None, None, None
         out = _LinearFn._backward(ctx, gy, g_alias)
         return out + (None, None, None)
@@ -514,148 +498,70 @@ class _LinearFn(torch.autograd.Function):
         add2 = add.reshape(-1, add.shape[-1]) if add is not None else None
         if add2 is not None and not (add2.is_contiguous() and add2.data_ptr() % 16 == 0 and add2.dtype == torch.float32):
             add2 = add2.contiguous().float()
-        fused = [False]                                      # did a kernel take ``add``?
-
-        def parked():
-            """The segment gradient waiting in this layer's slot, if the fused epilogue can take it (K columns, fp32)."""
-            slot = getattr(ctx, "slot", None)
-            g = slot.g if slot is not None else None
-            if g is None or not (g.dtype == torch.float32 and g.is_contiguous() and g.data_ptr() % 16 == 0 and g.dim() == 2
-                                 and g.shape[1] == x.shape[1] and slot.mapping.numel() == x.shape[0]):
-                return None
-            return g
-
-        def finish(gx):
-            if gx is not None and add is not None and not fused[0]:
-                gx = gx + add.reshape(gx.shape)
-            return gx
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = b_param is not None and ctx.needs_input_grad[2]
         gy2 = gy.reshape(-1, gy.shape[-1]).contiguous()
         M, K = x.shape
         N = weight.shape[0]
-        st = _lib.stream_ptr()
-        gx = gw = gb = None
+        gx = None
         if ctx.mode == "tile":
             if gy2.data_ptr() % 16:
                 gy2 = gy2.clone()
-            if need_w:
-                w_param._cgv_rank = (M, N, K)            # rows of this layer's weight-gradient problem (Trainer: rank update)
-            if (need_w and wgrad_queue.active and _is_direct(w_param) and w_param.grad.is_contiguous()
+            if not (need_w and wgrad_queue.active and _is_direct(w_param) and w_param.grad.is_contiguous()
                     and (not need_b or (_is_direct(b_param) and b_param.grad.is_contiguous())) and lib_has_rows(M, N, K)):
-                # under the trainer: no prologue launch -- act'(z) is applied in the operand loads of bwd_input and of the
-                # grouped weight-gradient launch, which also sums the bias (primitives.WeightGradQueue.launch)
-                if need_x:
-                    gx = torch.empty(M, K, dtype=torch.float32, device=gy.device)
-                    if (M <= 128 and N >= 4096 and _lib.load().cgv_skinny_bwd_input_supported(M, N, K)
-                            and not (M > 64 and _lib.split_workspace_ready())):
-                        # few rows, a very long reduction: the row-split kernel spreads the weight over ~300 blocks (64 bead
-                        # rows x 5400 columns: 13.8 us with its reduce against 14.3 us of the tile kernel).  From 65 rows
-                        # on the tile kernel wins once it splits each tile's reduction over 2-4 blocks (96 x 5400: 15.1
-                        # against 21.2 us, 128 x 5400: 20.0 / 26.0; unsplit 34.9: tools/bwd_input_bench.py)
-                        prod = getattr(ctx, "producer", None)
-                        if prod is not None and skinny_bwd_input_out(gy2, z if act != ACT_NONE else None, weight, add2, gx, M, N, K,
-                                                                     act, prod.saved_tensors[2], int(prod.act)):
-                            prod.act_done = True           # (its reduction launch stored the producing layer's g: see forward)
-                            fused[0] = True
-                        else:
-                            fused[0] = skinny_bwd_input(gy2, z if act != ACT_NONE else None, weight, gx, M, N, K, act, add=add2)
-                    elif parked() is not None:
-                        slot = ctx.slot
-                        g_seg = slot.take()
-                        _lib.call("cgv_tile_linear_bwd_input_act_add_bcast", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                                  _lib.ptr(weight), _lib.ptr(add2), _lib.ptr(g_seg), _lib.ptr(slot.mapping), _lib.ptr(slot.plan.rowptr_d),
-                                  int(slot.mean), _lib.ptr(gx), M, N, K, act, st)
-                        fused[0] = True
-                    elif getattr(ctx, "producer", None) is not None:
-                        # the stored gradient is the one of the producing layer's PRE-activation (see forward)
-                        prod = ctx.producer
-                        _lib.call("cgv_tile_linear_bwd_input_out", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                                  _lib.ptr(weight), _lib.ptr(add2), _lib.ptr(gx), M, N, K, act, _lib.ptr(prod.saved_tensors[2]),
-                                  int(prod.act), st)
-                        prod.act_done = True
-                        fused[0] = True
-                    elif add2 is not None:
-                        _lib.call("cgv_tile_linear_bwd_input_act_add", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                                  _lib.ptr(weight), _lib.ptr(add2), _lib.ptr(gx), M, N, K, act, st)
-                        fused[0] = True
-                    else:
-                        _lib.call("cgv_tile_linear_bwd_input_act", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                                  _lib.ptr(weight), _lib.ptr(gx), M, N, K, act, st)
-                    gx = finish(gx.reshape(gy.shape[:-1] + (K,)))
-                w_param._cgv_exch = w_param._cgv_rank = (M, N, K)
-                tw, acc_w, _ = _grad_target(w_param, weight)
-                tb, acc_b = None, acc_w
-                if need_b:
-                    b_param._cgv_exch = (M, N, K)
-                    tb, acc_b, _ = _grad_target(b_param, b_param)
-                if acc_b != acc_w:
-                    raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-                wgrad_queue.enqueue(gy2, x, z if act != ACT_NONE else None, act, tw, tb, acc_w)
-                return (gx if need_x else add), None, None, None
-            # g = gy * Swish'(z) and the bias column sums in one launch, then two reduction-split MFMA GEMMs
-            g2 = torch.empty_like(gy2) if act != ACT_NONE else gy2
-            tb, acc_b, gb = _grad_target(b_param, b_param) if need_b else (None, False, None)
-            if act != ACT_NONE or need_b:
-                _lib.call("cgv_dense_grad_prepare", _lib.ptr(gy2), _lib.ptr(z), _lib.ptr(g2) if act != ACT_NONE else None,
-                          _lib.ptr(tb), M, N, act, int(acc_b), st)
-            if need_x:
-                gx = torch.empty(M, K, dtype=torch.float32, device=gy.device)
-                _lib.call("cgv_tile_linear_bwd_input", _lib.ptr(g2), _lib.ptr(weight), _lib.ptr(gx), M, N, K, st)
-                gx = finish(gx.reshape(gy.shape[:-1] + (K,)))
-            if need_w:
-                tw, acc_w, gw = _grad_target(w_param, weight)
-                if wgrad_queue.active and gw is None and lib_has_rows(M, N, K):
-                    # under the trainer: one grouped MFMA launch for all layers of this kind (primitives.launch)
-                    wgrad_queue.enqueue(g2, x, None, ACT_NONE, tw, None, acc_w)
-                else:
-                    _lib.call("cgv_tile_linear_wgrad", _lib.ptr(g2), _lib.ptr(x), _lib.ptr(tw), M, N, K, int(acc_w), st)
-            return (gx if need_x else add), gw, gb, None
+                return _LinearFn._backward_prepared(ctx, gy, gy2, add, act, need_x, need_w, need_b)
+            # under the trainer: no prologue launch -- act'(z) is applied in the operand loads of bwd_input and of the
+            # grouped weight-gradient launch, which also sums the bias (primitives.WeightGradQueue.launch)
         if need_x:
             gx = torch.empty(M, K, dtype=torch.float32, device=gy.device)
-            if (M > 32 and (N <= 1024 or (N < 4096 and _lib.split_workspace_ready())) and gy2.data_ptr() % 16 == 0
-                    and _lib.load().cgv_tile_supported(M, N, K)):
-                # many bead rows (64 beads of the 2000-atom config): one launch of the tile kernel against the row-split
-                # kernel + its reduction -- 600 outputs 7.8 against 11.4 us, and, since the tile kernel splits a long
-                # reduction over 2-4 blocks per tile, 1200 / 1800 outputs 8.0 / 8.7 against 11.7 / 12.0 us (with an
-                # activation 10.6 / 15.2 at 1800); at 5400 the row split keeps the shape (13.8 against 14.3;
-                # tools/bwd_input_bench.py 0 64)
-                prod = getattr(ctx, "producer", None)
-                if prod is not None and prod.saved_tensors[2] is not None:
-                    _lib.call("cgv_tile_linear_bwd_input_out", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                              _lib.ptr(weight), _lib.ptr(add2), _lib.ptr(gx), M, N, K, act, _lib.ptr(prod.saved_tensors[2]),
-                              int(prod.act), st)
-                    prod.act_done = True                   # (see forward: the producing layer's launches run without an activation)
-                    fused[0] = True
-                elif add2 is not None:
-                    _lib.call("cgv_tile_linear_bwd_input_act_add", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                              _lib.ptr(weight), _lib.ptr(add2), _lib.ptr(gx), M, N, K, act, st)
-                    fused[0] = True
-                else:
-                    _lib.call("cgv_tile_linear_bwd_input_act", _lib.ptr(gy2), _lib.ptr(z) if act != ACT_NONE else None,
-                              _lib.ptr(weight), _lib.ptr(gx), M, N, K, act, st)
-            else:
-                prod = getattr(ctx, "producer", None)
-                if prod is not None and skinny_bwd_input_out(gy2, z if act != ACT_NONE else None, weight, add2, gx, M, N, K, act,
-                                                             prod.saved_tensors[2], int(prod.act)):
-                    prod.act_done = True                   # (see forward: the producing layer's launches run without an activation)
-                    fused[0] = True
-                else:
-                    fused[0] = skinny_bwd_input(gy2, z if act != ACT_NONE else None, weight, gx, M, N, K, act, add=add2)
-            gx = finish(gx.reshape(gy.shape[:-1] + (K,)))
+            kind = bwd_input_choice(M, N, K, _lib.split_workspace_ready(), ctx.bias_aligned, gy2.data_ptr() % 16 == 0)
+            # a segment gradient parked in this layer's slot goes into the tile kernel's epilogue on the tile family's
+            # layers (anything else spreads it by ordinary launches: _with_parked)
+            slot = getattr(ctx, "slot", None)
+            g = slot.g if (slot is not None and ctx.mode == "tile" and kind == "tile") else None
+            parked = None
+            if g is not None and (g.dtype == torch.float32 and g.is_contiguous() and g.data_ptr() % 16 == 0 and g.dim() == 2
+                                  and g.shape[1] == K and slot.mapping.numel() == M):
+                parked = slot.take()
+            fused = bwd_input_launch(kind, gy2, z, act, weight, gx, add2, slot, parked, getattr(ctx, "producer", None))
+            gx = gx.reshape(gy.shape[:-1] + (K,))
+            if add is not None and not fused:
+                gx = gx + add.reshape(gx.shape)
+        gw = gb = None
         if need_w:
-            # row count / shape of this layer's weight-gradient problem: the data-parallel trainer sorts the layers
-            # whose operand rows are cheaper to exchange than their gradients to the front of the arena
-            w_param._cgv_exch = w_param._cgv_rank = (M, N, K)
-            if b_param is not None:
-                b_param._cgv_exch = (M, N, K)
+            gw, gb = wgrad_sink(w_param, b_param, gy2, x, z, act, (M, N, K), like=weight, need_b=need_b)
+        return (gx if need_x else add), gw, gb, None
+
+    @staticmethod
+    def _backward_prepared(ctx, gy, gy2, add, act, need_x, need_w, need_b):
+        """Tile layers outside the trainer's grouped queue: g = gy * Swish'(z) and the bias column sums in one launch, then
+        two reduction-split MFMA GEMMs."""
+        x, weight, z = ctx.saved_tensors
+        w_param, b_param = ctx.params
+        M, K = x.shape
+        N = weight.shape[0]
+        st = _lib.stream_ptr()
+        gx = gw = None
+        if need_w:
+            w_param._cgv_rank = (M, N, K)            # rows of this layer's weight-gradient problem (Trainer: rank update)
+        g2 = torch.empty_like(gy2) if act != ACT_NONE else gy2
+        tb, acc_b, gb = _grad_target(b_param, b_param) if need_b else (None, False, None)
+        if act != ACT_NONE or need_b:
+            _lib.call("cgv_dense_grad_prepare", _lib.ptr(gy2), _lib.ptr(z), _lib.ptr(g2) if act != ACT_NONE else None,
+                      _lib.ptr(tb), M, N, act, int(acc_b), st)
+        if need_x:
+            gx = torch.empty(M, K, dtype=torch.float32, device=gy.device)
+            _lib.call("cgv_tile_linear_bwd_input", _lib.ptr(g2), _lib.ptr(weight), _lib.ptr(gx), M, N, K, st)
+            gx = gx.reshape(gy.shape[:-1] + (K,))
+            if add is not None:
+                gx = gx + add.reshape(gx.shape)
+        if need_w:
             tw, acc_w, gw = _grad_target(w_param, weight)
-            tb, acc_b, gb = _grad_target(b_param, b_param) if need_b else (None, acc_w, None)
-            if tb is not None and acc_b != acc_w:            # never on this model; keep semantics anyway
-                raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-            wgrad_queue.enqueue(gy2, x, z if act != ACT_NONE else None, act, tw, tb, acc_w)
-            if not (wgrad_queue.active and gw is None and gb is None):
-                wgrad_queue.flush()                          # immediate mode (no trainer / not arena-managed)
+            if wgrad_queue.active and gw is None and lib_has_rows(M, N, K):
+                # under the trainer: one grouped MFMA launch for all layers of this kind (primitives.launch)
+                wgrad_queue.enqueue(g2, x, None, ACT_NONE, tw, None, acc_w)
+            else:
+                _lib.call("cgv_tile_linear_wgrad", _lib.ptr(g2), _lib.ptr(x), _lib.ptr(tw), M, N, K, int(acc_w), st)
         return (gx if need_x else add), gw, gb, None
 
 
@@ -707,19 +613,7 @@ class _PairLinearFn(torch.autograd.Function):
         for g2, x2, z, act, w_param, b_param, need_w, need_b in (
                 (ga, xa, za, act_a, pa_w, pa_b, ctx.needs_input_grad[2], pa_b is not None and ctx.needs_input_grad[3]),
                 (gb, xb, zb, act_b, pb_w, pb_b, ctx.needs_input_grad[4], pb_b is not None and ctx.needs_input_grad[5])):
-            gw = gbias = None
-            if need_w:
-                w_param._cgv_exch = w_param._cgv_rank = (M, N, K)
-                if b_param is not None:
-                    b_param._cgv_exch = (M, N, K)
-                tw, acc_w, gw = _grad_target(w_param, w_param)
-                tb, acc_b, gbias = _grad_target(b_param, b_param) if need_b else (None, acc_w, None)
-                if tb is not None and acc_b != acc_w:
-                    raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-                wgrad_queue.enqueue(g2, x2, z if act != ACT_NONE else None, act, tw, tb, acc_w)
-                if not (wgrad_queue.active and gw is None and gbias is None):
-                    wgrad_queue.flush()
-            grads_w += [gw, gbias]
+            grads_w += wgrad_sink(w_param, b_param, g2, x2, z, act, (M, N, K), need_b=need_b) if need_w else (None, None)
         shape_a = None if gxa is None else gxa.reshape(xa.shape)
         return (shape_a if need_xa else None, (gxb if need_xb else None), grads_w[0], grads_w[1], grads_w[2], grads_w[3], None, None)
 
@@ -775,14 +669,13 @@ class _TilePairFn(torch.autograd.Function):
         prep = lambda g: None if g is None else g.reshape(M, N).contiguous()
         ga, gb = prep(g_a), prep(g_b)
         new = lambda: torch.empty(M, K, dtype=torch.float32, device=xa.device)
+        # (the pair's single products stay on the tile kernel at 65 - 128 rows x >= 4096 columns: never measured against the
+        # row split there)
+        kind = bwd_input_choice(M, N, K, _lib.split_workspace_ready(), long_row_split=False)
 
-        def single(g, z, w, add, act):
+        def single(g, z, w, add, act, parked=None):
             gx = new()
-            zp = _lib.ptr(z) if act != ACT_NONE else None
-            if add is not None:
-                _lib.call("cgv_tile_linear_bwd_input_act_add", _lib.ptr(g), zp, _lib.ptr(w), _lib.ptr(add), _lib.ptr(gx), M, N, K, act, st)
-            else:
-                _lib.call("cgv_tile_linear_bwd_input_act", _lib.ptr(g), zp, _lib.ptr(w), _lib.ptr(gx), M, N, K, act, st)
+            bwd_input_launch(kind, g, z, act, w, gx, add, slot, parked)
             return gx
         gxa = gxb = None
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
@@ -813,10 +706,7 @@ class _TilePairFn(torch.autograd.Function):
                 if gb_done:
                     pass
                 elif ga is not None and parked is not None and parked.dtype == torch.float32 and parked.is_contiguous() and parked.shape[1] == K:
-                    gxa = new()
-                    _lib.call("cgv_tile_linear_bwd_input_act_add_bcast", _lib.ptr(ga), _lib.ptr(za) if act_a != ACT_NONE else None, _lib.ptr(wa),
-                              _lib.ptr(add), _lib.ptr(parked), _lib.ptr(slot.mapping), _lib.ptr(slot.plan.rowptr_d), int(slot.mean),
-                              _lib.ptr(gxa), M, N, K, act_a, st)
+                    gxa = single(ga, za, wa, add, act_a, parked)
                 else:
                     gxa = single(ga, za, wa, add, act_a) if ga is not None else add
                     if parked is not None:
@@ -848,22 +738,9 @@ class _TilePairFn(torch.autograd.Function):
                 (gb, xb, zb, act_b, pb_w, pb_b, ctx.needs_input_grad[4], pb_b is not None and ctx.needs_input_grad[5])):
             gw = gbias = None
             if need_w and g2 is None:
-                # this layer's output left the loss: an arena-managed gradient is not pre-zeroed (see _LinearFn.backward)
-                for prm in (w_param, b_param):
-                    if prm is not None and _is_direct(prm) and prm._cgv_pending:
-                        prm.grad.zero_()
-                        prm._cgv_pending = False
+                zero_unreached((w_param, b_param))         # this layer's output left the loss
             elif need_w:
-                w_param._cgv_exch = w_param._cgv_rank = (M, N, K)
-                if b_param is not None:
-                    b_param._cgv_exch = (M, N, K)
-                tw, acc_w, gw = _grad_target(w_param, w_param)
-                tb, acc_b, gbias = _grad_target(b_param, b_param) if need_bias else (None, acc_w, None)
-                if tb is not None and acc_b != acc_w:
-                    raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-                wgrad_queue.enqueue(g2, x2, z if act != ACT_NONE else None, act, tw, tb, acc_w)
-                if not (wgrad_queue.active and gw is None and gbias is None):
-                    wgrad_queue.flush()
+                gw, gbias = wgrad_sink(w_param, b_param, g2, x2, z, act, (M, N, K), need_b=need_bias)
             grads_w += [gw, gbias]
         return (gxa if need_a else None, None if ctx.same else (gxb if need_b else None), grads_w[0], grads_w[1], grads_w[2], grads_w[3],
                 None, None, None)
@@ -973,19 +850,7 @@ class _MultiLinearFn(torch.autograd.Function):
             w_param, b_param = pws[j], pbs[j]
             need_w = ctx.needs_input_grad[2 + n + 2 * j]
             need_b = b_param is not None and ctx.needs_input_grad[2 + n + 2 * j + 1]
-            gw = gbias = None
-            if need_w:
-                w_param._cgv_exch = w_param._cgv_rank = (M, N, K)
-                if b_param is not None:
-                    b_param._cgv_exch = (M, N, K)
-                tw, acc_w, gw = _grad_target(w_param, w_param)
-                tb, acc_b, gbias = _grad_target(b_param, b_param) if need_b else (None, acc_w, None)
-                if tb is not None and acc_b != acc_w:
-                    raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-                wgrad_queue.enqueue(g2[j], x2[j], zs[j] if acts[j] != ACT_NONE else None, acts[j], tw, tb, acc_w)
-                if not (wgrad_queue.active and gw is None and gbias is None):
-                    wgrad_queue.flush()
-            grads_wb += [gw, gbias]
+            grads_wb += wgrad_sink(w_param, b_param, g2[j], x2[j], zs[j], acts[j], (M, N, K), need_b=need_b) if need_w else (None, None)
         return (None, None, *gxs, *grads_wb)
 
 
@@ -1103,8 +968,124 @@ def lib_has_rows(M, N, K) -> bool:
     return M >= 1 and N >= 4 and K >= 4 and N % 4 == 0 and K % 4 == 0
 
 
-def lib_tile_ok(M, N, K) -> bool:
-    return bool(_lib.load().cgv_tile_supported(M, N, K))
+FWD_ENTRY = {"decoder_dense": "cgv_decoder_dense_fwd", "skinny": "cgv_skinny_linear_fwd", "tile": "cgv_tile_linear_fwd"}
+
+
+def fwd_choice(M, N, K, bias_aligned=True, decoder_dense=True, wide_tiles=True) -> str:
+    """The forward kernel of a linear product of M rows: "decoder_dense", "skinny" or "tile" (``FWD_ENTRY``).
+    ``decoder_dense`` / ``wide_tiles``: the two rules of ``_LinearFn`` that the fused UpdateBlock does not apply."""
+    lib = _lib.load()
+    if lib.cgv_skinny_supported(M, N, K) and bias_aligned:
+        if decoder_dense and M <= 16 and N >= 64:
+            # few rows: 4-column blocks (N / 4 of them pull the weight) beat the skinny kernel's 16-column blocks
+            # (decoder forward 356 -> 343 us on chignolin: csrc/decoder_layer.hip, dec_dense_fwd_k)
+            return "decoder_dense"
+        if wide_tiles and M > 32 and N >= 4096 and lib.cgv_tile_supported(M, N, K):
+            # 33 - 64 rows and a very wide layer (64 beads x 5400 outputs): the tiles win (11.7 against 14.2 us)
+            return "tile"
+        return "skinny"
+    # 65 - 128 rows (a big bead batch) and at most 1200 outputs: the weight-streaming kernel with one 16-row block per thread
+    # block still beats the tiles (96 rows: 600 x 600 4.8 against 6.7 us, 600 x 1200 6.3 / 10.5, 1200 x 600 5.9 / 6.7; from
+    # 1800 outputs on the tiles win: tools/fwd_bench.py)
+    if M <= 128 and N <= 1200 and bias_aligned and lib.cgv_skinny_fwd_supported(M, N, K):
+        return "skinny"
+    return "tile"
+
+
+def bwd_input_choice(M, N, K, split_ready, bias_aligned=True, gy_aligned=True, short_tiles=True, long_row_split=True) -> str:
+    """The kernel of gx = (gy * act'(z)) W for a linear product of M rows: "skinny" (row-split kernel + its reduction) or
+    "tile".  ``split_ready``: _lib.split_workspace_ready() (the tile kernel may split its reduction, cgv_tile_bwd_input_plan).
+    ``short_tiles`` / ``long_row_split``: the rules of ``_LinearFn`` that the fused UpdateBlock / the tile pairs do not apply."""
+    lib = _lib.load()
+    if lib.cgv_skinny_supported(M, N, K) and bias_aligned:
+        # 33 - 64 rows (64 beads of the 2000-atom config): one launch of the tile kernel against the row-split kernel + its
+        # reduction -- 600 outputs 7.8 against 11.4 us, and, since the tile kernel splits a long reduction over 2-4 blocks per
+        # tile, 1200 / 1800 outputs 8.0 / 8.7 against 11.7 / 12.0 us (with an activation 10.6 / 15.2 at 1800); at 5400 the row
+        # split keeps the shape (13.8 against 14.3; tools/bwd_input_bench.py 0 64)
+        if (M > 32 and ((short_tiles and N <= 1024) or (N < 4096 and split_ready)) and gy_aligned
+                and lib.cgv_tile_supported(M, N, K)):
+            return "tile"
+        return "skinny"
+    if (long_row_split and M <= 128 and N >= 4096 and lib.cgv_skinny_bwd_input_supported(M, N, K)
+            and not (M > 64 and split_ready)):
+        # few rows, a very long reduction: the row-split kernel spreads the weight over ~300 blocks (64 bead rows x 5400
+        # columns: 13.8 us with its reduce against 14.3 us of the tile kernel).  From 65 rows on the tile kernel wins once it
+        # splits each tile's reduction over 2-4 blocks (96 x 5400: 15.1 against 21.2 us, 128 x 5400: 20.0 / 26.0; unsplit
+        # 34.9: tools/bwd_input_bench.py)
+        return "skinny"
+    return "tile"
+
+
+def bwd_input_launch(kind, gy2, z, act, weight, gx, add=None, slot=None, parked=None, producer=None) -> bool:
+    """gx [M, K] = add + (gy2 * act'(z)) W on the kernel ``kind`` (``bwd_input_choice``).  ``parked``: a segment gradient
+    taken from ``slot``, added spread over the rows in the tile kernel's store epilogue (its layout checked by the caller).
+    ``producer``: the node whose activated output is this layer's input (``_LinearFn.forward``) -- the stored gradient is
+    then the one of its pre-activation and ``producer.act_done`` is set when a kernel applied it.  Returns True when
+    ``add`` went in (False: the caller still has to add it)."""
+    M, K = gx.shape
+    N = weight.shape[0]
+    z = z if act != ACT_NONE else None
+    if kind == "skinny":
+        if producer is not None and skinny_bwd_input_out(gy2, z, weight, add, gx, M, N, K, act, producer.saved_tensors[2],
+                                                         int(producer.act)):
+            producer.act_done = True           # (its reduction launch stored the producing layer's g: see _LinearFn.forward)
+            return True
+        return skinny_bwd_input(gy2, z, weight, gx, M, N, K, act, add=add)
+    st = _lib.stream_ptr()
+    P = _lib.ptr
+    if parked is not None:
+        _lib.call("cgv_tile_linear_bwd_input_act_add_bcast", P(gy2), P(z), P(weight), P(add), P(parked), P(slot.mapping),
+                  P(slot.plan.rowptr_d), int(slot.mean), P(gx), M, N, K, act, st)
+    elif producer is not None:
+        _lib.call("cgv_tile_linear_bwd_input_out", P(gy2), P(z), P(weight), P(add), P(gx), M, N, K, act,
+                  P(producer.saved_tensors[2]), int(producer.act), st)
+        producer.act_done = True               # (see _LinearFn.forward: the producing layer's launches run without an activation)
+    elif add is not None:
+        _lib.call("cgv_tile_linear_bwd_input_act_add", P(gy2), P(z), P(weight), P(add), P(gx), M, N, K, act, st)
+    else:
+        _lib.call("cgv_tile_linear_bwd_input_act", P(gy2), P(z), P(weight), P(gx), M, N, K, act, st)
+        return False
+    return True
+
+
+def wgrad_sink(w_param, b_param, gy, x, z, act, shape, exch=True, like=None, need_b=True, stacked=None, flush=True):
+    """Hand one layer's weight / bias gradient problem  gW (+)= (gy * act'(z))^T x  to the grouped queue, writing into the
+    gradient arena where the parameters are arena-managed; returns (gw, gb) for autograd (None where written in place).
+    ``shape`` (M, N, K) tags the weight (``_cgv_rank``: rank-update layers) and, with ``exch``, weight and bias (``_cgv_exch``:
+    the data-parallel operand exchange orders the arena by it, trainer.py).  ``like``: the tensor a returned gradient is
+    shaped after (default the weight).  ``stacked``: the parameter stored right after ``w_param`` whose rows continue the
+    problem's (the UpdateBlock's [u_mat; v_mat] as ONE product).  ``flush=False``: the caller flushes once for all its
+    layers; else an immediate-mode queue (no trainer / not arena-managed) is flushed here."""
+    w_param._cgv_rank = shape
+    if exch:
+        w_param._cgv_exch = shape
+        if b_param is not None:
+            b_param._cgv_exch = shape
+    tw, acc_w, gw = _grad_target(w_param, w_param if like is None else like)
+    if stacked is not None:
+        stacked._cgv_rank = shape
+        _tv, acc_v, _ = _grad_target(stacked, stacked)
+        if acc_v != acc_w:
+            raise RuntimeError("stacked weights of one problem disagree on first-write / accumulate state")
+        n, k = w_param.shape
+        tw = torch.as_strided(tw, (n + stacked.shape[0], k), (k, 1))
+    tb, acc_b, gb = _grad_target(b_param, b_param) if (b_param is not None and need_b) else (None, acc_w, None)
+    if acc_b != acc_w:
+        raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
+    wgrad_queue.enqueue(gy, x, z if act != ACT_NONE else None, act, tw, tb, acc_w)
+    if flush and not (wgrad_queue.active and gw is None and gb is None):
+        wgrad_queue.flush()
+    return gw, gb
+
+
+def zero_unreached(params):
+    """The layer's output left the loss: its weight / bias gradient is zero.  Arena-managed (direct-write) parameters get no
+    zero fill at the start of a step (ParamArena.zero_grad only flags them pending), so the zero has to be written here --
+    otherwise last step's gradient would enter the norm, the clip and the update."""
+    for prm in params:
+        if _is_direct(prm) and prm._cgv_pending:
+            prm.grad.zero_()
+            prm._cgv_pending = False
 
 
 def skinny_bwd_input(gy2, z, weight, gx, M, N, K, act, stream=None, add=None) -> bool:

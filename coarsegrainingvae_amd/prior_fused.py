@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .decoder_fused import Slices, staged_edges
-from .primitives import ACT_NONE, ACT_SWISH, Swish, _grad_target, _is_direct, wgrad_queue
+from .primitives import ACT_NONE, ACT_SWISH, Swish, _grad_target, _is_direct, wgrad_queue, wgrad_sink
 
 _F32 = torch.float32
 PER_LAYER = 6           # W1 b1 W2 b2 Wd bd
@@ -115,14 +115,8 @@ class _PriorLoopFn(torch.autograd.Function):
             p2 = new(nF * fl)
             _lib.call("cgv_decoder_dense_bwd", _lib.ptr(p1), nb, fl, _lib.ptr(z1), ACT_SWISH, _lib.ptr(pW1.detach()), _lib.ptr(g_a1),
                       _lib.ptr(p2), fl, n, F, F, st)
-            for gy, x, z, act, pw, pb, shape in ((g_phi, a1, None, ACT_NONE, pW2, pb2, (n, 3 * F, F)), (g_a1, h_in, z1, ACT_SWISH, pW1, pb1, (n, F, F))):
-                tw, acc_w, _ = _grad_target(pw, pw)
-                tb, acc_b, _ = _grad_target(pb, pb)
-                if acc_b != acc_w:
-                    raise RuntimeError("weight and bias of one layer disagree on first-write / accumulate state")
-                wgrad_queue.enqueue(gy, x, z, act, tw, tb, acc_w)
-                pw._cgv_exch = pw._cgv_rank = shape
-                pb._cgv_exch = shape
+            wgrad_sink(pW2, pb2, g_phi, a1, None, ACT_NONE, (n, 3 * F, F), flush=False)
+            wgrad_sink(pW1, pb1, g_a1, h_in, z1, ACT_SWISH, (n, F, F), flush=False)
             gS = Slices(g_h, p2, nF, fl)
         gh_in = new(n, F)
         _lib.call("cgv_decoder_slices_to_dense", _lib.ptr(gS.base), _lib.ptr(gS.part), gS.n, gS.stride, _lib.ptr(gh_in), n, F, st)

@@ -230,3 +230,99 @@ def test_backward_input_plan_matches_what_the_mirror_assumes():
     assert plan(332, 1800, 600) == (1, 0) and plan(704, 1800, 600) == (1, 0)
     assert plan(2000, 1800, 600) == (1, 1) and plan(2000, 5400, 600) == (1, 1)      # stream-K: many rows, small output, long reduction
     assert plan(2000, 1800, 600, 2) == (1, 0) and plan(2000, 600, 600) == (1, 0)    # pairs and short reductions stay on the tiles
+
+
+@pytest.mark.parametrize("option", [None, ("streamk", 1), ("streamk", 2), ("streamk", 3), ("streamk", 16), ("bwd_input_waves", 8),
+                                    ("bwd_input_waves", 16), ("bwd_input_waves", 32), ("bwd_input_split", 1), ("bwd_input_split", 2)])
+def test_backward_input_plan_sweep_is_unchanged(options, option):
+    """cgv_tile_bwd_input_plan over the bench workloads' GEMM shapes and the row-count boundaries, at default and forced
+    options: the answers recorded before the plan and the launcher shared one rule (cgv::bwd_input_choice)."""
+    import ctypes as C
+    import json
+    from conftest import GOLDEN
+    lib = _lib.load()
+    with open(os.path.join(GOLDEN, "bwd_input_plan.json")) as f:
+        rec = json.load(f)
+    key = "default"
+    if option is not None:
+        options.set(*option)
+        key = f"{option[0]}={option[1]}"
+    shares, sk = C.c_int(), C.c_int()
+    got = []
+    for M in rec["rows"]:
+        for N in rec["cols"]:
+            for K in rec["reds"]:
+                for np_ in (1, 2):
+                    assert lib.cgv_tile_bwd_input_plan(M, N, K, np_, C.byref(shares), C.byref(sk)) == 0
+                    got.append(f"{shares.value}{sk.value}")
+    assert got == rec["plans"][key].split()
+
+
+# The bench workloads' linear products at F = 600 (profiles/r06_gemm_shapes.txt): bead rows 12 / 96 / 64, atom rows 332 / 704 /
+# 2000, and the row-count boundaries of the rules
+_CHOICE_ROWS = (12, 96, 64, 332, 704, 2000, 16, 17, 32, 33, 64, 65, 128, 129)
+_CHOICE_COLS = (600, 1200, 1800, 5400)
+_CHOICE_REDS = (600, 1200)
+
+
+def _rules_before_the_merge(lib):
+    """The kernel choices as each call site wrote them out before they shared primitives.fwd_choice / bwd_input_choice."""
+    sk, tile = lib.cgv_skinny_supported, lib.cgv_tile_supported
+
+    def linear_fwd(M, N, K):                                      # primitives._LinearFn._forward
+        mode = "skinny" if sk(M, N, K) else "tile"
+        if mode == "skinny" and M <= 16 and N >= 64:
+            return "decoder_dense"
+        few_rows = mode == "tile" and M <= 128 and N <= 1200
+        wide = mode == "skinny" and M > 32 and N >= 4096 and tile(M, N, K)
+        return "skinny" if ((mode == "skinny" and not wide) or few_rows) else "tile"
+
+    def dense_fwd(M, N, K):                                       # ops._dense_fwd
+        few_rows = M <= 128 and N <= 1200 and lib.cgv_skinny_fwd_supported(M, N, K)
+        return "skinny" if (sk(M, N, K) or few_rows) else "tile"
+
+    def linear_bwd(M, N, K, split):                               # primitives._LinearFn._backward_core
+        if sk(M, N, K):
+            return "tile" if (M > 32 and (N <= 1024 or (N < 4096 and split)) and tile(M, N, K)) else "skinny"
+        return "skinny" if (M <= 128 and N >= 4096 and lib.cgv_skinny_bwd_input_supported(M, N, K) and not (M > 64 and split)) else "tile"
+
+    def dense_bwd(M, N, K, split):                                # ops._dense_bwd_input
+        tile_wins = 32 < M <= 64 and N < 4096 and split and tile(M, N, K)
+        return "skinny" if ((sk(M, N, K) and not tile_wins) or (M <= 128 and N >= 4096 and lib.cgv_skinny_bwd_input_supported(M, N, K)
+                                                                 and not (M > 64 and split))) else "tile"
+    return linear_fwd, dense_fwd, linear_bwd, dense_bwd
+
+
+def test_linear_kernel_choice_keeps_every_call_sites_answers():
+    """primitives.fwd_choice / bwd_input_choice (pure: shapes, alignment, flags) give every call site the kernel it chose on
+    its own before: _LinearFn, the fused UpdateBlock (ops._dense_fwd / _dense_bwd_input) and the tile pairs' single
+    backward-input products -- with and without a split workspace."""
+    from coarsegrainingvae_amd.primitives import bwd_input_choice, fwd_choice
+    lib = _lib.load()
+    linear_fwd, dense_fwd, linear_bwd, dense_bwd = _rules_before_the_merge(lib)
+    for M in _CHOICE_ROWS:
+        for N in _CHOICE_COLS:
+            for K in _CHOICE_REDS:
+                assert fwd_choice(M, N, K) == linear_fwd(M, N, K), (M, N, K)
+                assert fwd_choice(M, N, K, decoder_dense=False, wide_tiles=False) == dense_fwd(M, N, K), (M, N, K)
+                for split in (False, True):
+                    assert bwd_input_choice(M, N, K, split) == linear_bwd(M, N, K, split), (M, N, K, split)
+                    assert bwd_input_choice(M, N, K, split, short_tiles=False) == dense_bwd(M, N, K, split), (M, N, K, split)
+                    if M > 64:                                   # _TilePairFn: tile-family shapes, always the tile kernel
+                        assert bwd_input_choice(M, N, K, split, long_row_split=False) == "tile", (M, N, K, split)
+    # the four places where the call sites differ, as named arguments
+    assert (fwd_choice(12, 600, 600), fwd_choice(12, 600, 600, decoder_dense=False)) == ("decoder_dense", "skinny")
+    assert fwd_choice(16, 600, 600) == "decoder_dense" and fwd_choice(17, 600, 600) == "skinny"
+    assert (fwd_choice(64, 5400, 600), fwd_choice(64, 5400, 600, wide_tiles=False)) == ("tile", "skinny")
+    assert fwd_choice(32, 5400, 600) == "skinny" and fwd_choice(33, 5400, 600) == "tile"
+    assert fwd_choice(128, 1200, 600) == "skinny" and fwd_choice(129, 1200, 600) == "tile" and fwd_choice(96, 1800, 600) == "tile"
+    for split in (False, True):
+        assert bwd_input_choice(64, 600, 600, split) == "tile"
+        assert bwd_input_choice(64, 600, 600, split, short_tiles=False) == ("tile" if split else "skinny")
+        assert bwd_input_choice(96, 5400, 600, split) == ("tile" if split else "skinny")
+        assert bwd_input_choice(96, 5400, 600, split, long_row_split=False) == "tile"
+    assert bwd_input_choice(32, 1200, 600, True) == "skinny" and bwd_input_choice(33, 1200, 600, True) == "tile"
+    assert bwd_input_choice(128, 5400, 600, False) == "skinny" and bwd_input_choice(129, 5400, 600, False) == "tile"
+    assert bwd_input_choice(64, 5400, 600, True) == "skinny" and bwd_input_choice(65, 5400, 600, True) == "tile"
+    # a misaligned bias / gradient takes the layer off the skinny family / the tile kernel, as _gemm_mode and the launch did
+    assert fwd_choice(12, 600, 600, bias_aligned=False) == "tile" and bwd_input_choice(64, 600, 600, True, gy_aligned=False) == "skinny"
