@@ -296,6 +296,7 @@ class WeightGradQueue:
     STRIP_SPLIT_MAX_ROWS = 96
     STRIP_SPLIT_MIN_ROWS = 64
     _strip_ws = {}
+    _strip_captured = []        # every workspace a stream capture recorded: never freed (see strip_launch)
 
     def strip_launch(self, table, n_problems, blocks, rows, tag):
         """The strip-layout store launch for the table ``strip_table`` has just built: on the bf16 matrix path with split
@@ -313,6 +314,11 @@ class WeightGradQueue:
                 # other launches: the buffer then comes from the graph's pool and stays referenced here, like every other
                 # tensor a captured step allocates)
                 ws = self._strip_ws[dev] = torch.empty(max(plane_bytes, 32 << 20), dtype=torch.uint8, device=dev)
+            if torch.cuda.is_current_stream_capturing() and not any(t is ws for t in self._strip_captured):
+                # a graph recorded this buffer's address and may be replayed after an eager launch with a larger plan has
+                # replaced it here: it must not go back to the allocator.  The queue cannot see when such a graph dies, so
+                # the buffer is kept for the process (buffers only grow: one per larger plan)
+                self._strip_captured.append(ws)
             _lib.call("cgv_grouped_wgrad_strip_split", _lib.ptr(table), n_problems, blocks, rows, max_k, _lib.ptr(ws), ws.numel(),
                       _lib.stream_ptr(), tag=tag)
         else:

@@ -431,6 +431,7 @@ class Trainer:
         self._rank_hi = 0             # arena floats [0, _rank_hi) belong to rank-update weights
         self._rank_numel = 0
         self._early_carry = []        # ranges of finished buckets below EARLY_MIN_FLOATS, waiting for the next boundary
+        self._rank_ws = None          # Gram workspace of the rank update's norm launch
         self._rank_ws2 = None         # Gram workspace of the MFMA rank update's norm launch
         self._rank_step = None        # this step's (table, problems, blocks, lds, items, max rows) once the Gram launch is out
         self._rank_mfma = None        # ([(kind, table, problems, blocks, rows)], problems, items) of the layers on the two-pass MFMA rank update
@@ -441,6 +442,7 @@ class Trainer:
         self.rank_steps_mfma = 0      # data-parallel steps whose many-row layers took the MFMA tile rank update
         self._pending = False
         self._side = None
+        self._warm = None             # side stream of capture()'s warm-up steps (one per trainer: the split workspace is per stream)
         self._dec_ranges = None
         self.betas, self.eps, self.max_norm = betas, eps, max_norm
         self.world = world_size
@@ -673,7 +675,11 @@ class Trainer:
                 self._forward(batch, eps_buf)
             torch.cuda.set_rng_state(rng, dev)
             _rng_block(dev).copy_(sample_rng)
-        side = torch.cuda.Stream()
+        if self._warm is None:
+            # ONE warm-up stream per trainer: _lib keeps a split workspace (64 MB) per stream for the life of the process,
+            # so a fresh stream per capture (re-captures after learning-rate changes) pinned another one each time
+            self._warm = torch.cuda.Stream(device=self.arena.p.device)
+        side = self._warm
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
@@ -705,8 +711,12 @@ class Trainer:
         tables = wgrad_queue.finish_capture()               # record tables: on the device before the first replay
         self._pending = pending_at_start                    # recorded, not run: the update it opens with is still due
         # the step's result tensors live in the graph's pool: a replay refreshes them in place
+        # "keep": the rank-update workspaces the graph recorded.  A later eager step may REPLACE one of them (a batch that
+        # does not fit the captured buffers runs eagerly, and with more rows its plan can need more room); the old tensor must
+        # not go back to the allocator while the graph still writes to its address (the queue's strip workspace: strip_launch)
+        keep = [t for t in (self._rank_ws, self._mfma_partial, self._rank_ws2) if t is not None]
         record = {"graph": graph, "batch": batch, "lr": self.lr, "eps": eps_buf, "tables": tables,
-                  "results": (self.last_loss, self.last_terms, self.last_out), "done": None}
+                  "results": (self.last_loss, self.last_terms, self.last_out), "done": None, "keep": keep}
         if _twin_of is not None:
             _twin_of["twin"] = record                       # the same step on a second set of batch buffers (enable_prefetch)
         else:
