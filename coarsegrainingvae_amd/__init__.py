@@ -15,5 +15,7 @@ from .model import CGequiVAE, CGprior, EquiEncoder, EquivariantDecoder, Equivari
 from .data import (CG_collate, CGDataset, batch_to, build_dataset, get_high_order_edge, get_higher_order_adj_matrix,
                    prepare_batch, random_rotation_matrices, synthetic_batch)
 from .train import KL, build_model, loop, loss_terms, train_step
+from .evaluate import (bond_radii, ensemble_batch, eval_sample_qualities, reconstruction_quality, sample_ensemble,
+                       sample_quality)
 
 __version__ = "0.1.0"

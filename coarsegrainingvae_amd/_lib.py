@@ -196,6 +196,8 @@ PROTOTYPES = {
     "cgv_rank_flat_plan": (_i, [_i, _i, _i, _i, _p, _p]),
     "cgv_grouped_wgrad_adam_flat": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _f, _f, _f, _f, _p, _p]),
     "cgv_grouped_wgrad_adam_mixed": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _f, _f, _f, _p, _p]),
+    "cgv_sample_quality_max_classes": (_i, []),
+    "cgv_sample_quality": (_i, [_p] * 6 + [_i] * 5 + [_p, _p, _p]),
 }
 
 

@@ -22,6 +22,9 @@ OBJDIR = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libcgvae_hip.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=fast", "-I", INCLUDE, "-I", CSRC]
+# per-source additions (after FLAGS, so they win): the sample-quality kernel compares bit-reproducible squared sums
+# against host-derived thresholds -- no product may fuse into a sum there
+SOURCE_FLAGS = {"sample_quality.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:
@@ -48,7 +51,7 @@ def _compile(src: str, force: bool) -> str:
     headers.append(os.path.join(INCLUDE, "cgvae_hip.h"))
     if not force and _newer(obj, [src] + headers):
         return obj
-    cmd = [_hipcc(), *FLAGS, "-x", "hip", "-c", src, "-o", obj]
+    cmd = [_hipcc(), *FLAGS, *SOURCE_FLAGS.get(os.path.basename(src), []), "-x", "hip", "-c", src, "-o", obj]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError(f"hipcc failed on {src}:\n{res.stderr[-4000:]}")

@@ -36,8 +36,10 @@ class GeomJob(C.Structure):
 
 
 # ----------------------------------------------------------------------------- K0
-def cutoff_threshold_sq(cutoff: float) -> float:
-    """Largest fp32 ``s`` with ``torch.sqrt(s) <= float32(cutoff)`` on THIS host.
+def cutoff_threshold_sq(cutoff: float, strict: bool = False) -> float:
+    """Largest fp32 ``s`` with ``torch.sqrt(s) <= float32(cutoff)`` on THIS host (``strict=True``: with
+    ``torch.sqrt(s) < float32(cutoff)`` -- the bond test of the reference's ``get_bond_graphs``, scripts/sampling.py:158-166;
+    the cutoff must be positive then).
 
     The reference tests ``sqrt(s) <= cutoff`` with the host's (not correctly rounded) fp32 sqrt
     (data.py:71-75).  Comparing the bit-reproducible squared sum against this threshold keeps
@@ -47,13 +49,16 @@ def cutoff_threshold_sq(cutoff: float) -> float:
     c = np.float32(cutoff)
     if not np.isfinite(c) or c < 0:
         raise ValueError("cutoff must be a finite non-negative number")
+    if strict and c == 0:
+        raise ValueError("the strict threshold needs a positive cutoff (no s has sqrt(s) < 0)")
     guess = np.float32(c) * np.float32(c)
     bits = int(np.array(guess, dtype=np.float32).view(np.uint32))
     lo, hi = max(bits - 64, 0), bits + 64
 
     pattern = np.arange(lo, hi + 1, dtype=np.uint32).view(np.float32).copy()
     # evaluated through the same vectorised torch.sqrt the reference's dense [n,n] call uses
-    window = (torch.sqrt(torch.from_numpy(pattern)) <= torch.tensor(c)).tolist()
+    roots = torch.sqrt(torch.from_numpy(pattern))
+    window = ((roots < torch.tensor(c)) if strict else (roots <= torch.tensor(c))).tolist()
     if not window[0] or window[-1]:
         raise RuntimeError("cutoff threshold search window does not bracket the cutoff")
     k = max(i for i, w in enumerate(window) if w)

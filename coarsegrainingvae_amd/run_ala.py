@@ -4,8 +4,8 @@ MI355X hot path.  Every flag keeps its name, type and default.  What is in scope
 training loop of one fold: model wiring (run_ala.py:184-209), Adam + ReduceLROnPlateau +
 early stopping (211-215, 232-284) and the CSV log columns (228-229, 252-258).
 
-Out of scope (SURVEY.md 2.1 rows 6, 7, 14): trajectory download / mdtraj loading, CG-mapping
-learners, k-fold evaluation metrics.  Frames come either from ``--synthetic`` (uniform random
+Out of scope (SURVEY.md 2.1 rows 6, 7): trajectory download / mdtraj loading, CG-mapping
+learners, k-fold cross-validation.  Frames come either from ``--synthetic`` (uniform random
 coordinates of the dataset's shape) or from ``-traj file.npz`` -- a trajectory
 converted offline by ``tools/traj_to_npz.py`` (xyz [T,n,3] in Angstrom, z [n], bonds, optional
 atom -> bead ``mapping``), which goes through the on-device ``build_dataset`` (datasets.py:459-506:
@@ -18,6 +18,18 @@ accepts ``cuda:N`` strings besides the reference's int.
         -dec_nconv 9 -enc_nconv 2 -lr 0.0001 -n_basis 600 -n_rbf 10 --synthetic
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1``;
 each rank trains on its shard of every batch (frames are independent graphs).
+
+After training (run_ala.py:286-408), on rank 0 and when the run did not fail, the test-time evaluation of
+``evaluate.py``: reconstruction quality of the first ``-nevals`` training batches (a flag the reference parses and
+never reads; here it caps the training frames evaluated, default 36 batches) and of the hold-out frames, the unaligned
+all-atom / heavy-atom RMSD, and ``-n_ensemble`` samples per hold-out frame from the prior (``--graph_eval``: with the
+bond-graph metrics; ``--reflectiontest``: on mirrored hold-out frames).  This driver trains ONE fold, so the hold-out
+frames are its validation indices -- there is no separate k-fold test split -- and ``test_KL`` / ``test_graph`` are the
+last epoch's validation terms.  Written to the log directory: ``cv_stats.csv`` (one row, the reference's columns,
+absent values as empty cells; a ``-traj`` file with elements that have no tabulated covalent radius gets no
+evaluation, with a message on stderr), ``test_all_rmsd*.txt`` / ``test_heavy_rmsd*.txt`` and ``samples.npz`` (sample, data,
+bead and reconstruction coordinates; the reference's xyz movies need ase and are out of scope).  The JSON summary
+carries the same numbers under ``"test_stats"``, with or without ``-logdir``.
 """
 from __future__ import annotations
 
@@ -173,6 +185,82 @@ def _batches(dataset, indices, batch_size, rank, world, device, prepared=None):
             yield cgdata.prepare_batch(collated, device, edge_slack=0.25 if prepared is not None else 0.0)
 
 
+def write_cv_stats(path, stats):
+    """cv_stats.csv (run_ala.py:404-405): one header line, one row; ``None`` is an empty cell."""
+    from .evaluate import CV_STATS_COLUMNS
+    with open(path, "w") as f:
+        f.write(",".join(CV_STATS_COLUMNS) + "\n")
+        f.write(",".join("" if stats.get(c) is None else str(stats[c]) for c in CV_STATS_COLUMNS) + "\n")
+
+
+def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch, logdir):
+    """run_ala.py:286-408 for one fold: reconstruction quality (train, capped by ``-nevals`` batches, and hold-out),
+    unaligned RMSDs, ensemble sampling of the hold-out frames.  Returns the ``test_stats`` dict."""
+    from . import evaluate as ev
+    present = sorted({int(e) for t in dataset.props["nxyz"] for e in t[:, 0].tolist()})
+    radii = None
+    if params["synthetic"]:
+        # synthetic frames carry random type labels 1..8, not chemistry: labels without a tabulated radius take carbon's
+        radii = {e: ev.COVALENT_RADII[6] for e in present if e not in ev.COVALENT_RADII}
+    else:
+        try:
+            ev.bond_radii(present)
+        except KeyError as err:
+            # a trajectory with elements outside the radius table: the bond-graph metrics are undefined for it -- say so
+            # and leave the trained model (already saved) without an evaluation rather than fail the run
+            print(f"evaluation skipped: {err.args[0]}", file=sys.stderr, flush=True)
+            return None
+    bs = max(int(params["batch_size"]), 1)
+
+    def batches(idx, cap=None):
+        starts = range(0, len(idx), bs)
+        for start in (list(starts)[:cap] if cap is not None else starts):
+            yield cgdata.CG_collate([dataset[i] for i in idx[start:start + bs]])
+
+    def unaligned(true_xyz, recon_xyz, z):
+        # run_ala.py:338-348 (frames of one molecule: the heavy filter is per atom of the concatenated frames)
+        if not len(true_xyz):
+            return None, None
+        d2 = np.power(recon_xyz - true_xyz, 2).sum(-1)
+        heavy = z != 1
+        return float(np.sqrt(d2.mean())), (float(np.sqrt(d2[heavy].mean())) if heavy.any() else float("nan"))
+
+    def z_of(idx, cap=None):
+        idx = idx[:cap * bs] if cap is not None else idx
+        return np.concatenate([dataset[i]["nxyz"][:, 0].numpy() for i in idx]) if idx else np.zeros(0)
+    cap = max(int(params["nevals"]), 0)
+    stats = {c: None for c in ev.CV_STATS_COLUMNS}
+    tr = ev.reconstruction_quality(batches(train_idx, cap), model, reflection=False, radii=radii)
+    stats["train_all_recon"], stats["train_heavy_recon"] = unaligned(tr[0], tr[1], z_of(train_idx, cap))
+    if last_epoch:
+        stats.update({"train_KL": last_epoch["train_KL"], "test_KL": last_epoch["val_KL"],
+                      "train_graph": last_epoch["train_graph"], "test_graph": last_epoch["val_graph"]})
+    samples = None
+    if val_idx:
+        te = ev.reconstruction_quality(batches(val_idx), model, reflection=params["reflectiontest"], radii=radii)
+        stats["test_all_recon"], stats["test_heavy_recon"] = unaligned(te[0], te[1], z_of(val_idx))
+        stats.update({"recon_all_valid_ratio": float(te[3]), "recon_heavy_valid_ratio": float(te[4]),
+                      "recon_all_ged": float(te[5]), "recon_heavy_ged": float(te[6])})
+        samples = ev.sample_ensemble([dataset[i] for i in val_idx], model, params["n_ensemble"],
+                                     reflection=params["reflectiontest"], graph_eval=params["graph_eval"], radii=radii)
+        if params["graph_eval"]:                                          # run_ala.py:370-385
+            all_rmsds, heavy_rmsds, valid, valid_all, ged, ged_all = samples[4:]
+            stats.update({"sample_heavy_valid_ratio": float(np.array(valid).mean()),
+                          "sample_all_valid_ratio": float(np.array(valid_all).mean()),
+                          "sample_all_rmsd": float(np.array(all_rmsds)[:, 0].mean()) if all_rmsds is not None else None,
+                          "sample_heavy_rmsd": float(np.array(heavy_rmsds)[:, 1].mean()) if heavy_rmsds is not None else None,
+                          "sample_heavy_ged": float(np.array(ged).mean()), "sample_all_ged": float(np.array(ged_all).mean())})
+    if logdir:
+        write_cv_stats(os.path.join(logdir, "cv_stats.csv"), stats)
+        if stats["test_all_recon"] is not None:                          # run_ala.py:350-352
+            for key, name in (("test_all_recon", "test_all_rmsd"), ("test_heavy_recon", "test_heavy_rmsd")):
+                np.savetxt(os.path.join(logdir, "{}{:.4f}.txt".format(name, stats[key])), np.array([stats[key]]))
+        if samples is not None and isinstance(samples[0], np.ndarray):
+            np.savez_compressed(os.path.join(logdir, "samples.npz"), sample_xyzs=samples[0], data_xyzs=samples[1],
+                                cg_xyzs=samples[2], recon_xyzs=samples[3], n_ensemble=params["n_ensemble"])
+    return stats
+
+
 def run(params) -> dict:
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -299,11 +387,14 @@ def run(params) -> dict:
         if failed:
             with open(os.path.join(logdir, "FAILED.txt"), "w") as f:
                 print("TRAINING FAILED", file=f)
+    test_stats = None
+    if rank == 0 and not failed:                                          # the other ranks wait at the teardown below
+        test_stats = evaluate_run(params, model, dataset, train_idx, val_idx, device, log_rows[-1] if log_rows else None, logdir)
     if world > 1:
         torch.distributed.destroy_process_group()
     return {"epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
-            "graph_replays": trainer.replays}
+            "graph_replays": trainer.replays, "test_stats": test_stats}
 
 
 def main(argv=None):

@@ -867,6 +867,39 @@ int cgv_grouped_wgrad_adam_mixed(const void* table_dev, int n_flat, int n_proble
                                  float* arena_v, float lr, float beta1, float beta2, float eps, const float* state,
                                  void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K12  sample quality -- replaces, for a whole evaluation chunk in one launch, get_bond_graphs / compare_graph /
+ * count_valid_graphs / compute_rmsd (scripts/sampling.py:120-239, called per sample by eval_sample_qualities,
+ * sampling.py:324-333, from sample_single and get_all_true_reconstructed_structures, scripts/utils.py:193-268), which
+ * build four dense [n,n] distance matrices per sample on the host.  Here no [n,n] tensor exists.
+ *   ref_xyz  [n_atoms,3]               the B = n_frames reference frames, frame f = rows frame_ptr[f] .. frame_ptr[f+1]
+ *   gen_xyz  [n_samples * n_atoms,3]   FRAME-major, sample-major inside a frame: sample k of frame f (n_f atoms) is rows
+ *                                      n_samples * frame_ptr[f] + k * n_f .. + n_f  (the order of the reference's
+ *                                      sample_xyzs, sampling.py:380, and of a disjoint-union decoder batch built that way)
+ *   cls      [n_atoms] int32           element class of each atom: index into thr_sq (clamped to [0, n_classes))
+ *   heavy    [n_atoms] int32           != 0: the atom belongs to the heavy-atom graph (z != 1, sampling.py:135-146)
+ *   thr_sq   [n_classes,n_classes]     SYMMETRIC; atoms i != j of classes a, b are bonded iff
+ *                                        s = (dx*dx + dy*dy) + dz*dz  <=  thr_sq[a][b]     (fp32, no FMA contraction)
+ *                                      with thr_sq = the largest fp32 whose host sqrt is < (r_a + r_b) * scale, computed by
+ *                                      the caller (graph.cutoff_threshold_sq(strict=True)): membership is bit-identical to
+ *                                      the reference's `sqrt(s) < cutoff` without depending on the device sqrt (as K0).
+ *   max_frame_atoms                    the largest n_f (sizes the grid; known to the caller, who built frame_ptr)
+ * Outputs per (frame f, sample k), row f * n_samples + k (both buffers are zeroed by the call):
+ *   counts [.,6] int32   diff_all, diff_heavy      entries where the sample's bond matrix differs from the reference's
+ *                        signed_all, signed_heavy  sum(ref - gen)  (the reference takes abs of the SIGNED sum, sampling.py:189)
+ *                        refsum_all, refsum_heavy  sum(ref)
+ *                        -- exact, independent of the order of the launch's blocks (integer vector atomics)
+ *   sums   [.,2] fp64    sum |gen - ref|^2 over all atoms / over heavy atoms, accumulated in double from
+ *                        double(gen) - double(ref) in a fixed order (bitwise reproducible)
+ * One launch for the chunk: a wave per (frame, sample, pair of 64-atom tiles), from 22-atom frames (one wave each) to
+ * 2000-atom frames (528 waves per sample).  n_classes <= cgv_sample_quality_max_classes(), n_f <= 32768,
+ * n_frames, n_samples <= 65535. */
+int cgv_sample_quality_max_classes(void);
+int cgv_sample_quality(const float* ref_xyz, const float* gen_xyz, const int32_t* frame_ptr /*[n_frames+1]*/,
+                       const int32_t* cls, const int32_t* heavy, const float* thr_sq, int n_frames, int n_atoms,
+                       int n_samples, int n_classes, int max_frame_atoms, int32_t* counts /*[n_frames*n_samples,6]*/,
+                       double* sums /*[n_frames*n_samples,2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
