@@ -4,8 +4,9 @@ MI355X hot path.  Every flag keeps its name, type and default.  What is in scope
 training loop of one fold: model wiring (run_ala.py:184-209), Adam + ReduceLROnPlateau +
 early stopping (211-215, 232-284) and the CSV log columns (228-229, 252-258).
 
-Out of scope: trajectory download / mdtraj loading, CG-mapping
-learners, k-fold cross-validation.  Frames come either from ``--synthetic`` (uniform random
+Out of scope: trajectory download / mdtraj loading, the graph-partition
+CG mappings (newman, backbonepartition), k-fold cross-validation.  ``-cg_method cgae`` on a ``-traj`` file without a
+``mapping`` learns the atom -> bead map on the device first (cgmap.py, datasets.py:190-249, 303-312).  Frames come either from ``--synthetic`` (uniform random
 coordinates of the dataset's shape) or from ``-traj file.npz`` -- a trajectory
 converted offline by ``tools/traj_to_npz.py`` (xyz [T,n,3] in Angstrom, z [n], bonds, optional
 atom -> bead ``mapping``), which goes through the on-device ``build_dataset`` (datasets.py:459-506:
@@ -43,6 +44,7 @@ from datetime import date
 import numpy as np
 import torch
 
+from . import cgmap
 from . import data as cgdata
 from .train import build_model, optim_dict
 from .trainer import Trainer
@@ -135,20 +137,19 @@ class EarlyStopping:
 def load_trajectory_dataset(params, device):
     """The non-synthetic branch of run_ala.py:124-181 for a file written by tools/traj_to_npz.py: frames (Angstrom),
     atomic numbers and the bond graph come from the file; the atom -> bead map is the file's ``mapping`` or, without
-    one, contiguous equal blocks of atoms (the reference's mapping learners -- cgae / newman / backbone partition,
-    datasets.py:252-330 -- are out of scope); then ``build_dataset`` on the device (datasets.py:459-506)."""
+    one, the map learned from the file's frames for ``-cg_method cgae`` (cgmap.select_mapping; under data parallel every
+    rank learns the same map from the same seed) and contiguous equal blocks of atoms for every other method (the
+    graph-partition mappings -- newman / backbone partition, datasets.py:277-301 -- are out of scope); then
+    ``build_dataset`` on the device (datasets.py:459-506).  Returns (dataset, mapping, learner's info or None)."""
     with np.load(params["traj"]) as f:
         need = {"xyz", "z", "bonds"}
         if not need.issubset(f.files):
             raise SystemExit(f"{params['traj']}: missing {sorted(need - set(f.files))} (see tools/traj_to_npz.py)")
         xyz, z, bonds = f["xyz"], f["z"], f["bonds"]
         mapping = f["mapping"] if "mapping" in f.files else None
+    # the learner sees the whole file (learn_map takes the trajectory, not the -ndata cut: datasets.py:190-197)
+    mapping, map_info = cgmap.select_mapping(params["cg_method"], mapping, xyz, params["n_cgs"], params["cgae_reg_weight"], device)
     xyz = xyz[: params["ndata"]]
-    n_atoms = xyz.shape[1]
-    if mapping is None:
-        if not params["n_cgs"]:
-            raise SystemExit("the trajectory file has no mapping: pass -n_cgs (contiguous equal blocks of atoms)")
-        mapping = (np.arange(n_atoms) * params["n_cgs"]) // n_atoms
     n_cgs = int(mapping.max()) + 1
     if params["n_cgs"] and params["n_cgs"] != n_cgs:
         raise SystemExit(f"-n_cgs {params['n_cgs']} but the file's mapping has {n_cgs} beads")
@@ -156,7 +157,7 @@ def load_trajectory_dataset(params, device):
     gen = torch.Generator().manual_seed(123)
     dataset = cgdata.build_dataset(mapping, xyz, params["atom_cutoff"], params["cg_cutoff"], z, bonds,
                                    order=params["edgeorder"], rotate=True, generator=gen, device=device)
-    return dataset, torch.as_tensor(mapping).long()
+    return dataset, torch.as_tensor(mapping).long(), map_info
 
 
 def _device(arg: str) -> torch.device:
@@ -283,8 +284,9 @@ def run(params) -> dict:
     torch.manual_seed(seed)
     np.random.seed(seed)
     beta = 0.0 if params["det"] else params["beta"]                      # run_ala.py:117-121
+    map_info = None
     if params.get("traj"):
-        dataset, mapping = load_trajectory_dataset(params, device)
+        dataset, mapping, map_info = load_trajectory_dataset(params, device)
     else:
         if params["dataset"] not in DATASET_SHAPES:
             raise SystemExit(f"unknown -dataset {params['dataset']}; known shapes: {sorted(DATASET_SHAPES)}")
@@ -394,7 +396,9 @@ def run(params) -> dict:
         torch.distributed.destroy_process_group()
     return {"epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
-            "graph_replays": trainer.replays, "test_stats": test_stats}
+            "graph_replays": trainer.replays, "test_stats": test_stats,
+            **({"cg_mapping": {k: map_info[k] for k in ("method", "steps", "seconds", "attempts", "loss_recon", "loss_reg")}}
+               if map_info else {})}
 
 
 def main(argv=None):

@@ -900,6 +900,41 @@ int cgv_sample_quality(const float* ref_xyz, const float* gen_xyz, const int32_t
                        int n_samples, int n_classes, int max_frame_atoms, int32_t* counts /*[n_frames*n_samples,6]*/,
                        double* sums /*[n_frames*n_samples,2]*/, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K13  coarse-graining map learner -- replaces the training loop of learn_map (CoarseGrainingVAE/datasets.py:204-249) on
+ * the auto-encoder of CoarseGrainingVAE/cgae.py:8-33, `steps` optimiser steps per call:
+ *   M = softmax(W + g), g = -log(E), E ~ Exp(1) (F.gumbel_softmax at temperature 1: the `tau` learn_map decrements never
+ *   reaches it, cgae.py:27 -- kept); M_norm = M / colsum(M); cg = M_norm^T X; recon = D^T cg; lift = M cg;
+ *   loss = mean((X - recon)^2) + reg_weight * mean_{b,i} sum_xyz (X - lift)^2   (datasets.py:229-231);
+ *   backward through all of it; torch.optim.Adam (bias correction, no weight decay) on W and D.
+ *   W, mW, vW [n,K]   assign_map and its Adam moments (updated in place)       D, mD, vD [K,n]   decode, likewise
+ *   frames [n_frames,n,3]   every frame minus its own mean over atoms (centred by the caller, once)
+ *   order  [order_len] int32   frame indices, whole epochs of n_train entries (a permutation of the training subset per
+ *                           epoch, drawn by the caller).  Step s of the schedule (Adam's step count s + 1) takes entries
+ *                           e * n_train + i * batch .. + min(batch, n_train - i * batch) with e = s / spe, i = s % spe,
+ *                           spe = ceil(n_train / batch): the last, partial batch of an epoch is kept and the means
+ *                           divide by its actual size.  The call runs steps step0 .. step0 + steps - 1.
+ *   noise  optional [steps,n,K]   explicit g of this call's steps (parity tests).  NULL: generated in the kernel, stateless,
+ *                           Philox4x32-10 with key = seed and counter = (atom, bead quad, step): word k % 4 of quad k / 4;
+ *                           top 23 bits b -> u = (b + 0.5) / 2^23 in the open interval; g = -log(-log(u)) in fp64, rounded once.
+ *                           cgv_cgae_noise writes exactly those numbers for steps step0 .. step0 + steps - 1 to out [steps,n,K].
+ *   loss_log [steps,2]      (loss_recon, loss_reg) of every step of this call
+ *   probe  optional         of the call's LAST step: M [n,K], dW [n,K], dD [K,n], cg_xyz [batch,K,3] (floats, in this order)
+ * form: CGV_CGAE_RESIDENT -- one workgroup keeps W, D and the moments in LDS for the whole call (one launch; needs
+ *   cgv_cgae_resident_fits(n, K, batch)); CGV_CGAE_STREAMED -- state in global memory, six launches per step.  Same form,
+ *   inputs and seed: bit-identical results, and a call of `steps` steps equals `steps` calls of one.
+ * workspace: cgv_cgae_workspace_bytes(n, K, batch, form), 256-byte aligned, contents need not survive between calls. */
+#define CGV_CGAE_RESIDENT 1
+#define CGV_CGAE_STREAMED 2
+int cgv_cgae_resident_fits(int n, int K, int batch);
+size_t cgv_cgae_workspace_bytes(int n, int K, int batch, int form);
+int cgv_cgae_steps(int form, float* W, float* D, float* mW, float* vW, float* mD, float* vD, const float* frames,
+                   int n_frames, const int32_t* order, int64_t order_len, int n_train, int batch, int n, int K,
+                   int64_t step0, int steps, float reg_weight, double lr, double beta1, double beta2, double eps,
+                   uint64_t seed, const float* noise, float* loss_log, float* probe, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int cgv_cgae_noise(uint64_t seed, int64_t step0, int steps, int n, int K, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
