@@ -198,6 +198,9 @@ PROTOTYPES = {
     "cgv_grouped_wgrad_adam_mixed": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _f, _f, _f, _p, _p]),
     "cgv_sample_quality_max_classes": (_i, []),
     "cgv_sample_quality": (_i, [_p] * 6 + [_i] * 5 + [_p, _p, _p]),
+    "cgv_ensemble_check_max_classes": (_i, []),
+    "cgv_ensemble_check_max_samples": (_i, []),
+    "cgv_ensemble_check": (_i, [_p] * 7 + [_i] * 6 + [_p, _p, _p]),
     "cgv_cgae_resident_fits": (_i, [_i, _i, _i]),
     "cgv_cgae_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cgv_cgae_steps": (_i, [_i] + [_p] * 7 + [_i, _p, C.c_int64, _i, _i, _i, _i, C.c_int64, _i, _f] + [C.c_double] * 4 +

@@ -1,0 +1,373 @@
+#!/usr/bin/env python3
+"""Backmapping: all-atom ensembles for a coarse-grained trajectory from a trained run, judged without a reference frame.
+
+``evaluate.sample_ensemble`` needs the all-atom frame of every bead frame (``nxyz``, an atom neighbour list, the bonds) and
+compares every sample with it.  A user who ran a CG simulation has bead coordinates only.  The decoder needs nothing
+else: per chunk of frames this module builds the bead graph, calls ``model.prior_net`` ONCE, draws the latents of all
+``frames x samples`` copies, calls ``model.decoder`` ONCE on the replicated bead graph (``evaluate.ensemble_batch``),
+launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No atom-level graph is built and
+``model(batch)`` is never called.  What can still be asked of the samples:
+
+  validity   does the sample have exactly the bond graph of the molecule's topology (K12's distance criterion
+             ``(r_a + r_b) * 1.3``, tested against a bond list)?   needs ``z`` and ``bonds``
+  diversity  the pairwise RMSD of the K samples of a frame -- the reference marks the place with
+             ``# compute sample diversity`` (scripts/sampling.py:296) and computes nothing there
+
+    python -m coarsegrainingvae_amd.backmap -model LOGDIR (-cg cg.npz | -traj atoms.npz) [-top top.npz] -n_samples K
+        -out out.npz [-frames_per_launch M] [-seed S] [--pair_rmsd] [--require_valid all|heavy -max_rounds R]
+
+``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
+the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
+are the topology unless ``-top`` (``z [n]``, ``bonds [Eb,2]``) is given.  The mapping comes from the run's
+``modelparams.json``.  Output: ``xyz [T,K,n,3]``, ``cg_xyz``, ``mapping``, ``n_samples``, ``seed``, ``diversity_all`` /
+``diversity_heavy [T]``, with a topology also ``valid_all`` / ``valid_heavy [T,K]`` and ``counts [T,K,4]`` (missing_all,
+extra_all, missing_heavy, extra_heavy), with ``--pair_rmsd`` ``pair_rmsd_all`` / ``pair_rmsd_heavy [T,K,K]``, with
+``--require_valid`` ``n_valid [T]``.  One JSON summary line goes to stdout.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import evaluate as ev
+from .train import build_model
+
+
+# ----------------------------------------------------------------------------- a trained run
+def read_params(logdir: str) -> dict:
+    path = os.path.join(logdir, "modelparams.json")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path}: not a run directory of run_ala (-logdir)")
+    with open(path) as f:
+        params = json.load(f)
+    if params.get("det"):
+        raise ValueError(f"{logdir} is a --det run: it was trained without the prior's latent terms, there is no prior "
+                         "to sample from")
+    if "mapping" not in params:
+        raise ValueError(f"{path} carries no atom -> bead mapping")
+    return params
+
+
+def load_run(logdir: str, device="cuda"):
+    """``(model, params)`` of a run directory written by ``run_ala``: ``modelparams.json`` (the flags, plus the atom ->
+    bead ``mapping``) and ``model.pt``, through ``train.build_model`` with ``strict=True``.  A ``--det`` run is refused."""
+    params = read_params(logdir)
+    model = build_model(params["n_basis"], params["n_rbf"], params["atom_cutoff"], params["cg_cutoff"], params["enc_nconv"],
+                        params["dec_nconv"], params["n_cgs"], activation=params.get("activation", "swish"), det=False,
+                        invariantdec=params.get("invariantdec", False), cg_mp=params.get("cg_mp", False), seed=None)
+    state = torch.load(os.path.join(logdir, "model.pt"), map_location="cpu")
+    model.load_state_dict(state, strict=True)
+    return model.to(device), params
+
+
+def check_topology(mapping, z=None, bonds=None) -> None:
+    """A topology must describe the molecule the run was trained on: as many atoms as the mapping."""
+    n = int(np.asarray(mapping).shape[0])
+    if z is not None and int(np.asarray(z).shape[0]) != n:
+        raise ValueError(f"the topology has {int(np.asarray(z).shape[0])} atoms, the run's mapping {n}")
+    if bonds is not None and np.size(bonds) and int(np.asarray(bonds).max()) >= n:
+        raise ValueError(f"the topology's bonds name atom {int(np.asarray(bonds).max())}, the run's mapping has {n} atoms")
+
+
+def canonical_bonds(bonds) -> np.ndarray:
+    """A bond list as K14 takes it: pairs ordered ``i < j``, sorted, every pair once (trajectory files list a bond in
+    either orientation).  Self bonds stay and are refused by the launch's validation."""
+    b = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
+    b = np.where((b[:, 0] <= b[:, 1])[:, None], b, b[:, ::-1])
+    return np.unique(b, axis=0) if b.shape[0] else b
+
+
+# ----------------------------------------------------------------------------- the sampler
+def _plan_for(z, sizes, device, scale, radii) -> ev.QualityPlan:
+    fp = np.concatenate([[0], np.cumsum(sizes)])
+    if z is None:
+        # elements unknown: one class that bonds nothing and no heavy atoms (all-atom diversity only)
+        return ev.QualityPlan(np.ones(int(fp[-1]), dtype=np.int64), fp, device, thresholds=np.zeros((1, 1), np.float32))
+    return ev.QualityPlan(np.tile(np.asarray(z).astype(np.int64), len(sizes)), fp, device, scale, radii)
+
+
+def backmap(model, cg_xyz, mapping, n_samples: int, cg_cutoff: float, *, z=None, bonds=None, eps=None,
+            frames_per_launch: int = 8, cg_bonds=None, radii: Optional[Dict[int, float]] = None, scale: float = 1.3) -> dict:
+    """``n_samples`` all-atom structures for every frame of the bead trajectory ``cg_xyz [T,N,3]`` (Angstrom) of one
+    molecule with the atom -> bead ``mapping [n]``.  ``cg_cutoff``: the radius of the bead graph the model was trained
+    with; ``cg_bonds [Ec,2]``: a fixed bead graph used instead (runs trained with ``--cg_radius_graph``:
+    ``data._bond_cg_graph`` of the molecule's bonds).  ``eps [T * n_samples * N, F]``: the latents' noise in output
+    order (frame, sample, bead) as for ``evaluate.sample_ensemble``; without it the device generator draws it
+    (``ops.reparam_sample``; bracket with ``ops.get_sample_rng_state`` / ``set_sample_rng_state``; the generator advances
+    per launch, so the same state reproduces the same structures for the same ``frames_per_launch``).
+
+    Returns a dict of host arrays: ``xyz [T,K,n,3]`` float32, ``cg_xyz [T,N,3]``, ``pair_rmsd_all [T,K,K]``,
+    ``diversity_all [T]`` (mean pairwise RMSD over ``k < l``; ``nan`` for one sample); with ``z`` (atomic numbers) also
+    ``pair_rmsd_heavy`` / ``diversity_heavy``; with ``z`` and ``bonds [Eb,2]`` (``i < j``, unique) also ``counts [T,K,4]``,
+    ``valid_all`` / ``valid_heavy [T,K]``.
+
+    Per chunk of ``frames_per_launch`` frames: one batched bead radius graph (the function
+    ``CGDataset.generate_neighbor_list`` uses: it reads the edge list back, its length being data dependent), one
+    ``model.prior_net`` call, one ``model.decoder`` call, one K14 launch, one read-back of the results.  Runs under
+    ``no_grad``; ``model.training`` is left as found."""
+    from . import ops
+    from .data import _batched_radius
+    from .graph import BatchGraph
+    K, M = int(n_samples), max(int(frames_per_launch), 1)
+    cg = torch.as_tensor(np.asarray(cg_xyz.detach().cpu() if torch.is_tensor(cg_xyz) else cg_xyz), dtype=torch.float32)
+    if cg.dim() != 3 or cg.shape[2] != 3:
+        raise ValueError("cg_xyz must be [frames, beads, 3]")
+    T, N = int(cg.shape[0]), int(cg.shape[1])
+    mapping = torch.as_tensor(np.asarray(mapping.detach().cpu() if torch.is_tensor(mapping) else mapping)).long().reshape(-1)
+    n = int(mapping.shape[0])
+    if K < 1:
+        raise ValueError("n_samples must be at least 1")
+    if n == 0 or int(mapping.min()) < 0 or int(mapping.max()) >= N:
+        raise ValueError(f"mapping must send every atom to one of the {N} beads")
+    check_topology(mapping, z, bonds)
+    if bonds is not None and z is None:
+        raise ValueError("a bond list needs the atomic numbers z (the bond cutoffs are per element pair)")
+    dev = ev._device_of(model)
+    bead_id = torch.arange(N).float()[:, None]                 # column 0 as build_dataset writes it
+    cg_nxyz = [torch.cat([bead_id, cg[t]], dim=1) for t in range(T)]
+    atoms = torch.empty(n, 4)                                  # ensemble_batch reads its row count only
+    fixed = torch.as_tensor(np.asarray(cg_bonds)).long().reshape(-1, 2) if cg_bonds is not None else None
+    plans, out = {}, {"xyz": np.empty((T, K, n, 3), np.float32), "cg_xyz": cg.numpy().copy(),
+                      "pair_rmsd_all": np.empty((T, K, K)), "diversity_all": np.empty(T)}
+    if z is not None:
+        out.update(pair_rmsd_heavy=np.empty((T, K, K)), diversity_heavy=np.empty(T))
+    if bonds is not None:
+        out.update(counts=np.empty((T, K, 4), np.int32), valid_all=np.empty((T, K), bool), valid_heavy=np.empty((T, K), bool))
+    eps_at = 0
+    was_training = model.training
+    try:
+        with torch.no_grad():
+            ev._settle(model)
+            for start in range(0, T, M):
+                B = min(M, T - start)
+                rows = cg_nxyz[start:start + B]
+                nbrs = [fixed] * B if fixed is not None else _batched_radius(rows, cg_cutoff, dev, True)
+                chunk = [{"CG_nxyz": rows[f], "nxyz": atoms, "CG_nbr_list": nbrs[f], "CG_mapping": mapping} for f in range(B)]
+                rep = ev.ensemble_batch(chunk, K, dev)
+                cg_rows = torch.cat(rows).to(dev)
+                offs = torch.arange(B)[:, None] * N
+                # the prior's bundle: bead graph and atom -> bead plan of the unreplicated chunk, an empty atom graph
+                graph = BatchGraph(torch.zeros(B * n, 3, device=dev), cg_rows[:, 1:], (mapping[None, :] + offs).reshape(-1).to(dev),
+                                   torch.zeros(0, 2, dtype=torch.int64, device=dev),
+                                   torch.cat([nb + f * N for f, nb in enumerate(nbrs)]).to(dev))
+                mu, sigma = model.prior_net(cg_rows[:, 0], graph.cg_xyz, graph.cg_nbrs, graph=graph)
+                mu_r, sigma_r = mu[rep["src_bead"]], sigma[rep["src_bead"]]
+                if eps is not None:
+                    e = eps[eps_at:eps_at + mu_r.shape[0]].to(dev)
+                    eps_at += mu_r.shape[0]
+                    H = e.mul(sigma_r).add_(mu_r)
+                else:
+                    H = ops.reparam_sample(mu_r.contiguous(), sigma_r.contiguous())
+                g_rep = rep["_graph"]
+                gen = model.decoder(g_rep.cg_xyz, rep["CG_nbr_list"], H, H, rep["CG_mapping"], rep["num_CGs"], graph=g_rep)
+                if B not in plans:                             # one molecule: the plan depends on the chunk's frame count only
+                    plan = _plan_for(z, [n] * B, dev, scale, radii)
+                    plans[B] = (plan, ev.BondList(bonds, plan) if bonds is not None else None)
+                plan, bond_list = plans[B]
+                raw = ev.ensemble_check(gen, K, plan, bond_list)
+                gen_h, counts_h, sums_h = ev._read_back([gen, raw.counts, raw.pair_sums])
+                out["xyz"][start:start + B] = gen_h.reshape(B, K, n, 3)
+                for f in range(B):
+                    chk = ev.assemble_ensemble_check(counts_h[f], sums_h[f], n, int(plan.n_heavy[f]))
+                    t = start + f
+                    out["pair_rmsd_all"][t], out["diversity_all"][t] = chk.pair_rmsd_all, chk.diversity_all
+                    if z is not None:
+                        out["pair_rmsd_heavy"][t], out["diversity_heavy"][t] = chk.pair_rmsd_heavy, chk.diversity_heavy
+                    if bonds is not None:
+                        out["counts"][t], out["valid_all"][t], out["valid_heavy"][t] = counts_h[f], chk.valid_all, chk.valid_heavy
+    finally:
+        model.train(was_training)
+    out["n_samples"] = K
+    return out
+
+
+def backmap_valid(model, cg_xyz, mapping, n_samples: int, cg_cutoff: float, *, z, bonds, which: str = "all",
+                  max_rounds: int = 4, **kw) -> dict:
+    """``backmap`` that keeps valid samples only (``which``: the ``all``-atom or the ``heavy``-atom bond graph).  After
+    the first draw, every frame with fewer than K valid samples gets K fresh draws per round, for at most ``max_rounds``
+    rounds; valid samples are kept in draw order and a full frame is never drawn again.  A frame still short at the end
+    is filled with the invalid draws of its last round and stays flagged in ``valid_*``.  The checks of the returned
+    ensembles come from one final K14 pass over them.  Extra entries: ``n_valid [T]`` and ``n_valid_rounds [rounds,T]``
+    (after the first draw and after every redraw).  One read-back per round and chunk, one for the final pass."""
+    if which not in ("all", "heavy"):
+        raise ValueError("which must be 'all' or 'heavy'")
+    if kw.get("eps") is not None:
+        raise ValueError("backmap_valid draws its own noise")
+    K = int(n_samples)
+    cg = np.asarray(cg_xyz.detach().cpu() if torch.is_tensor(cg_xyz) else cg_xyz, dtype=np.float32)
+    first = backmap(model, cg, mapping, K, cg_cutoff, z=z, bonds=bonds, **kw)
+    T, n = cg.shape[0], first["xyz"].shape[2]
+    kept = [first["xyz"][t][first["valid_" + which][t]] for t in range(T)]      # valid samples, draw order
+    spare = [first["xyz"][t][~first["valid_" + which][t]] for t in range(T)]    # the last round's invalid draws
+    history = [np.array([min(len(k), K) for k in kept])]
+    for _ in range(max(int(max_rounds), 0)):
+        short = [t for t in range(T) if len(kept[t]) < K]
+        if not short:
+            break
+        more = backmap(model, cg[short], mapping, K, cg_cutoff, z=z, bonds=bonds, **kw)
+        for i, t in enumerate(short):
+            ok = more["valid_" + which][i]
+            kept[t] = np.concatenate([kept[t], more["xyz"][i][ok]])[:K]
+            spare[t] = more["xyz"][i][~ok]
+        history.append(np.array([min(len(k), K) for k in kept]))
+    xyz = np.stack([np.concatenate([kept[t], spare[t][:K - len(kept[t])]]) if len(kept[t]) < K else kept[t] for t in range(T)])
+    out = _check_only(model, xyz, cg, z, bonds, kw.get("frames_per_launch", 8), kw.get("radii"), kw.get("scale", 1.3))
+    out.update(n_valid=history[-1], n_valid_rounds=np.stack(history), n_samples=K)
+    return out
+
+
+def _check_only(model, xyz, cg, z, bonds, frames_per_launch, radii, scale) -> dict:
+    """K14 over finished ensembles ``xyz [T,K,n,3]``: the entries of ``backmap``'s result."""
+    T, K, n = xyz.shape[:3]
+    dev, M = ev._device_of(model), max(int(frames_per_launch), 1)
+    out = {"xyz": xyz, "cg_xyz": cg.copy(), "pair_rmsd_all": np.empty((T, K, K)), "diversity_all": np.empty(T),
+           "pair_rmsd_heavy": np.empty((T, K, K)), "diversity_heavy": np.empty(T), "counts": np.empty((T, K, 4), np.int32),
+           "valid_all": np.empty((T, K), bool), "valid_heavy": np.empty((T, K), bool)}
+    plans = {}
+    for start in range(0, T, M):
+        B = min(M, T - start)
+        if B not in plans:
+            plan = _plan_for(z, [n] * B, dev, scale, radii)
+            plans[B] = (plan, ev.BondList(bonds, plan))
+        plan, bond_list = plans[B]
+        raw = ev.ensemble_check(torch.from_numpy(xyz[start:start + B].reshape(-1, 3)).to(dev), K, plan, bond_list)
+        counts_h, sums_h = ev._read_back([raw.counts, raw.pair_sums])
+        for f in range(B):
+            chk, t = ev.assemble_ensemble_check(counts_h[f], sums_h[f], n, int(plan.n_heavy[f])), start + f
+            out["pair_rmsd_all"][t], out["diversity_all"][t] = chk.pair_rmsd_all, chk.diversity_all
+            out["pair_rmsd_heavy"][t], out["diversity_heavy"][t] = chk.pair_rmsd_heavy, chk.diversity_heavy
+            out["counts"][t], out["valid_all"][t], out["valid_heavy"][t] = counts_h[f], chk.valid_all, chk.valid_heavy
+    return out
+
+
+# ----------------------------------------------------------------------------- command line
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m coarsegrainingvae_amd.backmap", description="all-atom ensembles for a "
+                                "coarse-grained trajectory from a trained run, with reference-free checks")
+    p.add_argument("-model", type=str, required=True, help="run directory of run_ala (modelparams.json, model.pt)")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("-cg", type=str, help=".npz with cg_xyz [T,N,3] in Angstrom")
+    src.add_argument("-traj", type=str, help="tools/traj_to_npz.py file: coarse-grained with the run's mapping, then backmapped")
+    p.add_argument("-top", type=str, default=None, help=".npz with z [n] and bonds [Eb,2] (default: those of -traj)")
+    p.add_argument("-n_samples", type=int, required=True)
+    p.add_argument("-out", type=str, required=True)
+    p.add_argument("-frames_per_launch", type=int, default=8)
+    p.add_argument("-seed", type=int, default=0, help="seed of the device sample generator")
+    p.add_argument("-device", type=str, default="0")
+    p.add_argument("--pair_rmsd", action="store_true", default=False, help="also write pair_rmsd_all / pair_rmsd_heavy [T,K,K]")
+    p.add_argument("--require_valid", choices=("all", "heavy"), default=None,
+                   help="keep valid samples only, redrawing short frames (needs a topology)")
+    p.add_argument("-max_rounds", type=int, default=4, help="redraw rounds of --require_valid")
+    return p
+
+
+def _npz(path: str, need) -> dict:
+    if not os.path.exists(path):
+        raise SystemExit(f"{path}: no such file")
+    with np.load(path, allow_pickle=False) as f:
+        missing = sorted(set(need) - set(f.files))
+        if missing:
+            raise SystemExit(f"{path}: missing {missing}")
+        return {k: f[k] for k in f.files}
+
+
+def read_inputs(args, params, device=None) -> dict:
+    """The CLI's input files as ``cg_xyz``, ``z``, ``bonds`` (``None`` where absent), checked against the run's mapping.
+    ``-traj`` frames are coarse-grained on ``device`` (``ops.scatter_mean`` over the mapping, no rotation)."""
+    mapping = np.asarray(params["mapping"], dtype=np.int64)
+    n, N = mapping.shape[0], int(mapping.max()) + 1
+    z = bonds = None
+    if args.cg:
+        cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
+    else:
+        f = _npz(args.traj, ["xyz", "z", "bonds"])
+        xyz, z, bonds = np.asarray(f["xyz"], dtype=np.float32), f["z"], f["bonds"]
+        if xyz.ndim != 3 or xyz.shape[1:] != (n, 3):
+            raise SystemExit(f"{args.traj}: xyz is {xyz.shape}, the run's mapping has {n} atoms")
+        from .ops import scatter_mean
+        T = xyz.shape[0]
+        index = (torch.from_numpy(mapping).to(device)[None, :] + N * torch.arange(T, device=device)[:, None]).reshape(-1)
+        cg = scatter_mean(torch.from_numpy(xyz).to(device).reshape(T * n, 3).contiguous(), index, dim=0,
+                          dim_size=T * N).reshape(T, N, 3).cpu().numpy()
+    if args.top:
+        f = _npz(args.top, ["z", "bonds"])
+        z, bonds = f["z"], f["bonds"]
+    if cg.ndim != 3 or cg.shape[1:] != (N, 3):
+        raise SystemExit(f"cg_xyz is {cg.shape}, the run's mapping has {N} beads")
+    try:
+        check_topology(mapping, z, bonds)
+    except ValueError as err:
+        raise SystemExit(str(err))
+    if bonds is not None:
+        bonds = canonical_bonds(bonds)
+    if args.require_valid and bonds is None:
+        raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
+    if params.get("cg_radius_graph") and bonds is None:
+        raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
+    return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping}
+
+
+def run(args) -> dict:
+    from . import ops
+    from .data import _bond_cg_graph
+    from .run_ala import _device
+    params = read_params(args.model)
+    device = _device(str(args.device))
+    torch.cuda.set_device(device)
+    torch.set_num_threads(min(torch.get_num_threads(), 8))
+    inp = read_inputs(args, params, device)
+    model, params = load_run(args.model, device)
+    mapping, z, bonds = inp["mapping"], inp["z"], inp["bonds"]
+    radii = None
+    if z is not None:
+        try:
+            ev.bond_radii(sorted(set(np.asarray(z).astype(np.int64).tolist())))
+        except KeyError as err:
+            if not params.get("synthetic"):
+                raise SystemExit(err.args[0])
+            # synthetic frames carry random type labels, not chemistry: as run_ala's evaluation, carbon's radius
+            radii = {int(e): ev.COVALENT_RADII[6] for e in set(np.asarray(z).astype(np.int64).tolist()) if int(e) not in ev.COVALENT_RADII}
+    cg_bonds = None
+    if params.get("cg_radius_graph"):
+        cg_bonds = _bond_cg_graph(torch.from_numpy(bonds), torch.from_numpy(mapping), mapping.shape[0], int(mapping.max()) + 1)
+    ops.set_sample_rng_state(device, torch.tensor([ops.sample_seed(args.seed), 0, 0], dtype=torch.int64))
+    kw = dict(z=z, bonds=bonds, frames_per_launch=args.frames_per_launch, cg_bonds=cg_bonds, radii=radii)
+    torch.cuda.synchronize(device)
+    t0 = time.time()
+    if args.require_valid:
+        res = backmap_valid(model, inp["cg_xyz"], mapping, args.n_samples, params["cg_cutoff"], which=args.require_valid,
+                            max_rounds=args.max_rounds, **kw)
+    else:
+        res = backmap(model, inp["cg_xyz"], mapping, args.n_samples, params["cg_cutoff"], **kw)
+    seconds = time.time() - t0
+    keep = ["xyz", "cg_xyz", "valid_all", "valid_heavy", "counts", "diversity_all", "diversity_heavy", "n_valid"]
+    if args.pair_rmsd:
+        keep += ["pair_rmsd_all", "pair_rmsd_heavy"]
+    arrays = {k: res[k] for k in keep if k in res}
+    arrays.update(mapping=mapping, n_samples=np.int64(args.n_samples), seed=np.int64(args.seed))
+    np.savez_compressed(args.out, **arrays)
+    T, K = res["xyz"].shape[:2]
+
+    def mean(key):
+        if key not in res:
+            return None
+        v = np.asarray(res[key], dtype=np.float64)
+        return float(np.nanmean(v)) if np.isfinite(v).any() else None
+    return {"frames": int(T), "samples": int(T * K), "seconds": seconds, "samples_per_s": T * K / max(seconds, 1e-9),
+            "valid_all_ratio": mean("valid_all"), "valid_heavy_ratio": mean("valid_heavy"),
+            "diversity_all": mean("diversity_all"), "diversity_heavy": mean("diversity_heavy"), "out": args.out}
+
+
+def main(argv=None):
+    print(json.dumps(run(build_parser().parse_args(argv))))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -22,9 +22,9 @@ OBJDIR = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libcgvae_hip.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=fast", "-I", INCLUDE, "-I", CSRC]
-# per-source additions (after FLAGS, so they win): the sample-quality kernel compares bit-reproducible squared sums
-# against host-derived thresholds -- no product may fuse into a sum there
-SOURCE_FLAGS = {"sample_quality.hip": ["-ffp-contract=off"]}
+# per-source additions (after FLAGS, so they win): the sample-quality kernels compare bit-reproducible squared sums
+# (csrc/sq_dist.h) against host-derived thresholds -- no product may fuse into a sum there
+SOURCE_FLAGS = {"sample_quality.hip": ["-ffp-contract=off"], "ensemble_check.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -141,6 +141,94 @@ def sample_quality(ref_xyz: torch.Tensor, gen_xyz: torch.Tensor, z=None, frame_p
     return RawQuality(counts, sums)
 
 
+# ----------------------------------------------------------------------------- reference-free checks (K14)
+RawEnsembleCheck = namedtuple("RawEnsembleCheck", "counts pair_sums")   # [B,K,4] int32, [B,K,K,2] float64 (device tensors)
+MISSING_ALL, EXTRA_ALL, MISSING_HEAVY, EXTRA_HEAVY = range(4)
+EnsembleCheck = namedtuple("EnsembleCheck", "valid_all valid_heavy missing_all extra_all missing_heavy extra_heavy "
+                                            "pair_rmsd_all pair_rmsd_heavy diversity_all diversity_heavy")
+
+
+def validate_bonds(bonds, sizes, bond_ptr=None):
+    """The topology of a K14 launch as host arrays ``(bonds [Eb,2] int32, bond_ptr [B+1] int32)``.  ``bonds`` holds atom
+    ids local to their frame; without ``bond_ptr`` the one list belongs to every frame (a trajectory of one molecule).
+    Raises ``ValueError`` unless every pair has ``i < j``, occurs once in its frame and lies inside the frame: the
+    kernel's ``missing = Eb - H``, ``extra = P - H`` count on it."""
+    sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+    b = _host_ints(bonds).reshape(-1, 2)
+    B = sizes.shape[0]
+    if bond_ptr is None:
+        ptr = np.arange(B + 1, dtype=np.int64) * b.shape[0]
+        b = np.tile(b, (B, 1))
+    else:
+        ptr = _host_ints(bond_ptr)
+        if ptr.shape[0] != B + 1 or ptr[0] != 0 or ptr[-1] != b.shape[0] or np.any(np.diff(ptr) < 0):
+            raise ValueError("bond_ptr must be the [B+1] prefix sum of bonds per frame, ending at len(bonds)")
+    frame_of = np.repeat(np.arange(B), np.diff(ptr))
+    if np.any(b[:, 0] >= b[:, 1]):
+        raise ValueError("bonds must be pairs (i, j) with i < j")
+    if b.shape[0] and (b.min() < 0 or np.any(b[:, 1] >= sizes[frame_of])):
+        raise ValueError("bonds hold atom ids outside their frame")
+    if b.shape[0] and np.unique(np.column_stack([frame_of, b]), axis=0).shape[0] != b.shape[0]:
+        raise ValueError("bonds must list every pair once")
+    return b.astype(np.int32), ptr.astype(np.int32)
+
+
+class BondList:
+    """A validated topology on the device for the frames of one ``QualityPlan`` (``validate_bonds``)."""
+
+    def __init__(self, bonds, plan: QualityPlan, bond_ptr=None):
+        b, ptr = validate_bonds(bonds, plan.sizes, bond_ptr)
+        self.n_bonds, self.n_frames = int(b.shape[0]), plan.n_frames
+        pack = torch.from_numpy(np.concatenate([ptr, b.reshape(-1)])).to(plan.device)
+        self.bond_ptr, self.bonds = pack[:plan.n_frames + 1], pack[plan.n_frames + 1:]
+
+
+def ensemble_check(gen_xyz: torch.Tensor, n_samples: int, plan: QualityPlan, bonds, bond_ptr=None) -> RawEnsembleCheck:
+    """Raw outputs of K14 as device tensors for the frames of ``plan``: ``counts [B,K,4]`` int32 (``MISSING_ALL ..
+    EXTRA_HEAVY``: unordered atom pairs of the topology that the sample does not bond / that it bonds outside the
+    topology) and ``pair_sums [B,K,K,2]`` float64 (sum over all / heavy atoms of the squared distance between samples
+    k and l).  ``gen_xyz [K*N,3]`` is frame-major, sample-major inside a frame, as for ``sample_quality``.  ``bonds``:
+    ``[Eb,2]`` frame-local atom ids with ``i < j`` (``bond_ptr [B+1]``: per-frame lists; without it the list belongs to
+    every frame), a ``BondList`` built before, or ``None``: no topology -- the counts stay zero.  One launch."""
+    K = int(n_samples)
+    lib = _lib.load()
+    if K > int(lib.cgv_ensemble_check_max_samples()):
+        raise ValueError(f"{K} samples per frame in one launch (the kernel holds {lib.cgv_ensemble_check_max_samples()})")
+    gen = gen_xyz.detach().contiguous().float()
+    if tuple(gen.shape) != (K * plan.n_atoms, 3):
+        raise ValueError(f"expected gen_xyz [{K * plan.n_atoms},3], got {tuple(gen.shape)}")
+    if bonds is not None and not isinstance(bonds, BondList):
+        bonds = BondList(bonds, plan, bond_ptr)
+    if bonds is not None and bonds.n_frames != plan.n_frames:
+        raise ValueError("the BondList was built for another set of frames")
+    counts = torch.empty(plan.n_frames, K, 4, dtype=torch.int32, device=gen.device)
+    pair_sums = torch.empty(plan.n_frames, K, K, 2, dtype=torch.float64, device=gen.device)
+    if counts.numel():
+        _lib.call("cgv_ensemble_check", _lib.ptr(gen), _lib.ptr(plan.frame_ptr), _lib.ptr(plan.cls), _lib.ptr(plan.heavy),
+                  _lib.ptr(plan.thr_sq), _lib.ptr(bonds.bond_ptr) if bonds is not None else None,
+                  _lib.ptr(bonds.bonds) if bonds is not None and bonds.n_bonds else None, plan.n_frames, plan.n_atoms, K,
+                  plan.n_classes, plan.max_atoms, bonds.n_bonds if bonds is not None else 0, _lib.ptr(counts),
+                  _lib.ptr(pair_sums), _lib.stream_ptr(), tag="ensemble_check")
+    return RawEnsembleCheck(counts, pair_sums)
+
+
+def assemble_ensemble_check(counts, pair_sums, n_atoms: int, n_heavy: int) -> EnsembleCheck:
+    """ONE frame's K14 outputs (``counts [K,4]``, ``pair_sums [K,K,2]``) as an ``EnsembleCheck``: ``valid_* [K]`` bool
+    (missing + extra == 0), the four count columns, ``pair_rmsd_* [K,K] = sqrt(sum / n)`` and ``diversity_*``, the mean
+    pairwise RMSD over ``k < l`` -- ``nan`` for a single sample, and for the heavy graph without heavy atoms."""
+    counts = np.asarray(counts).astype(np.int64).reshape(-1, 4)
+    K = counts.shape[0]
+    sums = np.asarray(pair_sums, dtype=np.float64).reshape(K, K, 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rmsd_all = np.sqrt(sums[..., 0] / np.float64(n_atoms))
+        rmsd_heavy = np.sqrt(sums[..., 1] / np.float64(n_heavy)) if n_heavy else np.full((K, K), np.nan)
+    upper = np.triu_indices(K, 1)
+    mean = lambda m: float(m[upper].mean()) if K > 1 else float("nan")
+    return EnsembleCheck(counts[:, MISSING_ALL] + counts[:, EXTRA_ALL] == 0, counts[:, MISSING_HEAVY] + counts[:, EXTRA_HEAVY] == 0,
+                         counts[:, MISSING_ALL], counts[:, EXTRA_ALL], counts[:, MISSING_HEAVY], counts[:, EXTRA_HEAVY],
+                         rmsd_all, rmsd_heavy, mean(rmsd_all), mean(rmsd_heavy))
+
+
 # ----------------------------------------------------------------------------- host assembly (pure functions)
 def assemble_sample_qualities(counts, sums, n_atoms: int, n_heavy: int):
     """The reference's 6-tuple of ``eval_sample_qualities`` for ONE frame (sampling.py:324-333) from the kernel's

@@ -935,6 +935,39 @@ int cgv_cgae_steps(int form, float* W, float* D, float* mW, float* vW, float* mD
                    size_t workspace_bytes, void* stream);
 int cgv_cgae_noise(uint64_t seed, int64_t step0, int steps, int n, int K, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K14  ensemble check -- reference-free quality of generated ensembles: what is left to ask when only bead coordinates
+ * exist (backmapping a coarse-grained trajectory) and K12 has no frame to compare with.  The reference marks the place
+ * with `# compute sample diversity` (scripts/sampling.py:296) and computes nothing there.
+ *   gen_xyz, frame_ptr, cls, heavy, thr_sq, max_frame_atoms    exactly as K12 (same layout, same bond test
+ *                                      s = (dx*dx + dy*dy) + dz*dz <= thr_sq[a][b], fp32, no FMA contraction)
+ *   bond_ptr [n_frames+1] int32        prefix sum of bonds per frame, ending at n_bonds (all zero: no bonds)
+ *   bonds    [n_bonds,2]  int32        the topology: atom ids LOCAL to their frame, i < j, every pair once, ids < n_f.
+ *                                      The CALLER guarantees this (the counting identity below needs unique pairs);
+ *                                      an entry outside it counts as a missing bond.
+ *                                      bond_ptr == NULL: no topology -- counts stay zero, only pair_sums are computed;
+ *                                      cls, thr_sq and bonds may then be NULL, and heavy too (heavy sums stay zero).
+ * Outputs (both buffers are zeroed by the call):
+ *   counts    [n_frames,n_samples,4] int32   missing_all, extra_all, missing_heavy, extra_heavy: unordered atom pairs that
+ *                        are a topology bond but not within the cutoff / within the cutoff but no topology bond; the heavy
+ *                        columns restrict to pairs of two heavy atoms.  Computed as missing = Eb - H, extra = P - H from
+ *                        P = pairs i < j within the cutoff (all-pairs pass, tiled as K12) and H = topology bonds within
+ *                        the cutoff (a pass over the bond list); integer vector atomics, exact in any order.
+ *                        A sample is valid iff missing + extra == 0.
+ *   pair_sums [n_frames,n_samples,n_samples,2] fp64   [f,k,l,0] = sum over the frame's atoms of |x_k - x_l|^2,
+ *                        [f,k,l,1] the same over heavy atoms; double(x_k) - double(x_l), added in atom order by one lane:
+ *                        bitwise reproducible, exactly symmetric, zero diagonal, both halves written.
+ * One launch for the chunk.  n_samples <= cgv_ensemble_check_max_samples() (1024), n_classes <=
+ * cgv_ensemble_check_max_classes() (= K12's), n_f <= 32768, n_frames <= 65535; beyond a limit the call fails
+ * (CGV_E_BADARG, cgv_last_error_string) -- nothing is clamped. */
+int cgv_ensemble_check_max_classes(void);
+int cgv_ensemble_check_max_samples(void);
+int cgv_ensemble_check(const float* gen_xyz, const int32_t* frame_ptr /*[n_frames+1]*/, const int32_t* cls,
+                       const int32_t* heavy, const float* thr_sq, const int32_t* bond_ptr /*[n_frames+1]*/,
+                       const int32_t* bonds /*[n_bonds,2]*/, int n_frames, int n_atoms, int n_samples, int n_classes,
+                       int max_frame_atoms, int n_bonds, int32_t* counts /*[n_frames*n_samples,4]*/,
+                       double* pair_sums /*[n_frames*n_samples*n_samples,2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
