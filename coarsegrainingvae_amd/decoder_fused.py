@@ -12,7 +12,9 @@ next phase as *slices* (``Slices``: base + one partial per block) and are added 
 Numerics: the same formulas in the same per-edge order as the per-block kernels; products are exact-fp32 MFMA chains;
 slice sums add in a fixed order.  Used for bead graphs of at most 16 nodes when every parameter is arena-managed
 (under ``Trainer`` from the second step on); the per-block path (blocks.py) remains the reference implementation and
-the fallback -- ``tests/test_full_size_parity.py::test_fused_decoder_loop_equals_per_block_path`` compares the two.
+the fallback -- ``tests/test_full_size_parity.py::test_fused_decoder_loop_equals_per_block_path`` compares the two over
+whole training steps, ``tests/test_decoder_loop_fp64.py`` compares both, tensor by tensor and with every message term
+live, with a float64 reference of the loop.
 """
 from __future__ import annotations
 

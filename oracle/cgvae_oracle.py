@@ -135,7 +135,7 @@ def linear(x: Tensor, P: Dict[str, Tensor], key: str, bias: bool = True) -> Tens
 def painn_rbf(dist: Tensor, n_rbf: int, cutoff: float) -> Tensor:
     """modules.py:148-172."""
     d = dist.unsqueeze(-1)
-    n = torch.arange(1, n_rbf + 1).float()
+    n = torch.arange(1, n_rbf + 1).to(d.dtype)       # fp32 input: .float() as modules.py; fp64 input keeps an fp64 coef
     coef = n * np.pi / cutoff
     denom = torch.where(d == 0, torch.tensor(1.0), d)
     num = torch.where(d == 0, coef, torch.sin(coef * d))

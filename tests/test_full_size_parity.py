@@ -32,6 +32,20 @@ def rel_err(got, ref):
     return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
+def _grad_ranges(tr, model):
+    """(name, offset, numel) of every parameter in the trainer's arena."""
+    names = {id(p): n for n, p in model.named_parameters()}
+    return [(names.get(id(p), f"#{k}"), o, p.numel()) for k, (o, p) in enumerate(zip(tr.arena.offsets, tr.arena.params))]
+
+
+def _assert_each_parameter_close(g1, g0, views, tol, what):
+    """The whole-arena comparison again, one parameter at a time: each gradient on its OWN scale (a small one -- a filter
+    bias, b1' -- cannot hide behind the largest weight gradient)."""
+    for name, o, m in views:
+        e = rel_err(g1[o:o + m], g0[o:o + m])
+        assert e <= tol, f"{what}: grad {name}: relative error {e:.3e} > {tol:.1e}"
+
+
 def _setup(workload, frames, F, enc=None, dec=None, seed=0):
     w = dict(cg.data.WORKLOADS[workload])
     enc, dec = enc or w["enc_nconv"], dec or w["dec_nconv"]
@@ -414,11 +428,13 @@ def test_fused_decoder_loop_equals_per_block_path(workload, frames, F, dec, fat,
             if k == 1:
                 grads = tr.arena.g.clone()
         assert decoder_fused.calls - calls0 == (2 if fused else 0)          # steps 2 and 3 (the first one builds the arena)
-        runs.append((losses, grads, tr.arena.p.clone(), [n for n, _ in model.named_parameters()]))
-    (l1, g1, p1, _), (l0, g0, p0, _) = runs
+        runs.append((losses, grads, tr.arena.p.clone(), _grad_ranges(tr, model)))
+    (l1, g1, p1, views), (l0, g0, p0, views0) = runs
     for a, b in zip(l1, l0):
         assert abs(a - b) <= 1e-6 * abs(b), (l1, l0)
     assert rel_err(g1, g0) <= 1e-5
+    assert views == views0
+    _assert_each_parameter_close(g1, g0, views, 1e-5, "fused against per-block")
     assert float((p1 - p0).abs().max()) <= 2e-2 * 1e-4 * 3 or rel_err(p1, p0) <= 1e-6
 
 
@@ -456,13 +472,15 @@ def test_channel_group_decoder_at_its_limits(n_atoms, n_cgs, frames, F, n_rbf, c
             n_edges = int(batch["_graph"].cg.n_edges)
             if fused and n_edges >= 1:
                 assert decoder_fused.calls - calls0 == 2, (n_edges, n_beads)      # the channel-group path did run
-            runs.append((losses, grads, tr.arena.p.clone(), n_edges))
-        (l1, g1, p1, n_edges), (l0, g0, p0, _) = runs
+            runs.append((losses, grads, tr.arena.p.clone(), n_edges, _grad_ranges(tr, model)))
+        (l1, g1, p1, n_edges, views), (l0, g0, p0, _, views0) = runs
         if (n_cgs, frames) == (16, 1):
             assert n_edges == 240
         for a, b in zip(l1, l0):
             assert abs(a - b) <= 2e-6 * abs(b), (l1, l0)
         assert rel_err(g1, g0) <= 2e-5
+        assert views == views0
+        _assert_each_parameter_close(g1, g0, views, 2e-5, "fused against per-block")
         assert float((p1 - p0).abs().max()) <= 2e-2 * 1e-4 * 3 or rel_err(p1, p0) <= 1e-6
     finally:
         cg.data.WORKLOADS.pop(name, None)
