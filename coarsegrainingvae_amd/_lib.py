@@ -201,6 +201,15 @@ PROTOTYPES = {
     "cgv_ensemble_check_max_classes": (_i, []),
     "cgv_ensemble_check_max_samples": (_i, []),
     "cgv_ensemble_check": (_i, [_p] * 7 + [_i] * 6 + [_p, _p, _p]),
+    "cgv_internal_hist_max_features": (_i, []),
+    "cgv_internal_hist_max_pairs": (_i, []),
+    "cgv_internal_hist_max_bins": (_i, []),
+    "cgv_internal_hist_max_bins2": (_i, []),
+    "cgv_internal_hist_max_atoms": (_i, []),
+    "cgv_internal_hist_max_staged_atoms": (_i, []),
+    "cgv_internal_hist_feature_tile": (_i, [_i]),
+    "cgv_internal_hist_pair_tile": (_i, [_i]),
+    "cgv_internal_hist": (_i, [_p] * 4 + [_i] * 6 + [C.c_double] * 2 + [_p] * 3),
     "cgv_cgae_resident_fits": (_i, [_i, _i, _i]),
     "cgv_cgae_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cgv_cgae_steps": (_i, [_i] + [_p] * 7 + [_i, _p, C.c_int64, _i, _i, _i, _i, C.c_int64, _i, _f] + [C.c_double] * 4 +

@@ -15,6 +15,7 @@ launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No a
 
     python -m coarsegrainingvae_amd.backmap -model LOGDIR (-cg cg.npz | -traj atoms.npz) [-top top.npz] -n_samples K
         -out out.npz [-frames_per_launch M] [-seed S] [--pair_rmsd] [--require_valid all|heavy -max_rounds R]
+        [--dist_stats [-ref atoms.npz]]
 
 ``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
 the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
@@ -23,6 +24,11 @@ are the topology unless ``-top`` (``z [n]``, ``bonds [Eb,2]``) is given.  The ma
 ``diversity_heavy [T]``, with a topology also ``valid_all`` / ``valid_heavy [T,K]`` and ``counts [T,K,4]`` (missing_all,
 extra_all, missing_heavy, extra_heavy), with ``--pair_rmsd`` ``pair_rmsd_all`` / ``pair_rmsd_heavy [T,K,K]``, with
 ``--require_valid`` ``n_valid [T]``.  One JSON summary line goes to stdout.
+
+``--dist_stats``: do the generated structures reproduce the distribution of all-atom data?  ``distributions.compare`` of
+all ``T * K`` of them against the frames of ``-ref`` (a ``tools/traj_to_npz.py`` file with the topology's atom order;
+default: the frames of ``-traj``): per-feature and per-(phi, psi) Jensen-Shannon divergences with their noise floor go to
+``dist_stats.json`` next to ``-out``, their means into the summary line under ``"dist_stats"``.  Needs a topology.
 """
 from __future__ import annotations
 
@@ -265,6 +271,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--require_valid", choices=("all", "heavy"), default=None,
                    help="keep valid samples only, redrawing short frames (needs a topology)")
     p.add_argument("-max_rounds", type=int, default=4, help="redraw rounds of --require_valid")
+    p.add_argument("--dist_stats", action="store_true", default=False,
+                   help="compare the internal-coordinate distributions of the output with -ref; writes dist_stats.json next to -out")
+    p.add_argument("-ref", type=str, default=None, help="all-atom tools/traj_to_npz.py file, same atom order (default: the frames of -traj)")
     return p
 
 
@@ -283,7 +292,10 @@ def read_inputs(args, params, device=None) -> dict:
     ``-traj`` frames are coarse-grained on ``device`` (``ops.scatter_mean`` over the mapping, no rotation)."""
     mapping = np.asarray(params["mapping"], dtype=np.int64)
     n, N = mapping.shape[0], int(mapping.max()) + 1
-    z = bonds = None
+    z = bonds = ref_xyz = None
+    dist_stats = getattr(args, "dist_stats", False)
+    if getattr(args, "ref", None) and not dist_stats:
+        raise SystemExit("-ref is the reference of --dist_stats")
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
@@ -293,6 +305,7 @@ def read_inputs(args, params, device=None) -> dict:
             raise SystemExit(f"{args.traj}: xyz is {xyz.shape}, the run's mapping has {n} atoms")
         from .ops import scatter_mean
         T = xyz.shape[0]
+        ref_xyz = xyz if dist_stats else None
         index = (torch.from_numpy(mapping).to(device)[None, :] + N * torch.arange(T, device=device)[:, None]).reshape(-1)
         cg = scatter_mean(torch.from_numpy(xyz).to(device).reshape(T * n, 3).contiguous(), index, dim=0,
                           dim_size=T * N).reshape(T, N, 3).cpu().numpy()
@@ -309,9 +322,21 @@ def read_inputs(args, params, device=None) -> dict:
         bonds = canonical_bonds(bonds)
     if args.require_valid and bonds is None:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
+    if dist_stats:
+        if bonds is None:
+            raise SystemExit("--dist_stats needs a topology (-top, or the z / bonds of -traj)")
+        if args.ref:
+            f = _npz(args.ref, ["xyz", "z"])
+            ref_xyz = np.asarray(f["xyz"], dtype=np.float32)
+            if ref_xyz.ndim != 3 or ref_xyz.shape[1:] != (n, 3):
+                raise SystemExit(f"{args.ref}: xyz is {ref_xyz.shape}, the topology has {n} atoms")
+            if not np.array_equal(np.asarray(f["z"]).astype(np.int64).reshape(-1), np.asarray(z).astype(np.int64).reshape(-1)):
+                raise SystemExit(f"{args.ref}: z differs from the topology's (the reference must list the same atoms in the same order)")
+        if ref_xyz is None or ref_xyz.shape[0] < 2:
+            raise SystemExit("--dist_stats needs reference frames: -ref file.npz (or -traj as the source), at least two")
     if params.get("cg_radius_graph") and bonds is None:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
-    return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping}
+    return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if dist_stats else {})}
 
 
 def run(args) -> dict:
@@ -354,6 +379,13 @@ def run(args) -> dict:
     arrays.update(mapping=mapping, n_samples=np.int64(args.n_samples), seed=np.int64(args.seed))
     np.savez_compressed(args.out, **arrays)
     T, K = res["xyz"].shape[:2]
+    dist = {}
+    if args.dist_stats:
+        from . import distributions
+        stats = distributions.compare(inp["ref_xyz"], res["xyz"].reshape(T * K, -1, 3), z, bonds, device=device)
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "dist_stats.json"), "w") as f:
+            json.dump(stats, f)
+        dist = {"dist_stats": distributions.summary_of(stats)}
 
     def mean(key):
         if key not in res:
@@ -362,7 +394,7 @@ def run(args) -> dict:
         return float(np.nanmean(v)) if np.isfinite(v).any() else None
     return {"frames": int(T), "samples": int(T * K), "seconds": seconds, "samples_per_s": T * K / max(seconds, 1e-9),
             "valid_all_ratio": mean("valid_all"), "valid_heavy_ratio": mean("valid_heavy"),
-            "diversity_all": mean("diversity_all"), "diversity_heavy": mean("diversity_heavy"), "out": args.out}
+            "diversity_all": mean("diversity_all"), "diversity_heavy": mean("diversity_heavy"), "out": args.out, **dist}
 
 
 def main(argv=None):

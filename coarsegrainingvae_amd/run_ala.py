@@ -53,7 +53,8 @@ DATASET_SHAPES = {"dipeptide": 22, "chignolin": 166, "pentapeptide": 94}   # ato
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser()
+    p = argparse.ArgumentParser(epilog="after the evaluation: --dist_eval compares the internal-coordinate distributions of the "
+                                "hold-out frames with their prior samples and writes dist_stats.json (build_extras_parser)")
     p.add_argument("-logdir", type=str)
     p.add_argument("-device", type=str, default="0")        # reference: int CUDA ordinal (run_ala.py:421)
     p.add_argument("-n_cgs", type=int)
@@ -96,6 +97,17 @@ def build_parser() -> argparse.ArgumentParser:
                    help="random-coordinate frames of the dataset's shape (no trajectories offline)")
     p.add_argument("-traj", type=str, default=None,
                    help="trajectory file from tools/traj_to_npz.py (xyz [T,n,3], z [n], bonds [Eb,2], optional mapping [n])")
+    return p
+
+
+def build_extras_parser() -> argparse.ArgumentParser:
+    """Switches of analyses that run after the reference's evaluation.  They are kept apart from ``build_parser`` -- the
+    reference's flag surface plus this build's run switches, which ``modelparams.json`` records -- and are parsed first
+    by ``main``; what they do not know goes on to ``build_parser``."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--dist_eval", action="store_true", default=False,
+                   help="after the evaluation, compare the internal-coordinate distributions of the hold-out frames with "
+                        "their prior samples (distributions.compare): dist_stats.json in the log directory")
     return p
 
 
@@ -259,7 +271,27 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
         if samples is not None and isinstance(samples[0], np.ndarray):
             np.savez_compressed(os.path.join(logdir, "samples.npz"), sample_xyzs=samples[0], data_xyzs=samples[1],
                                 cg_xyzs=samples[2], recon_xyzs=samples[3], n_ensemble=params["n_ensemble"])
+    if params.get("dist_eval"):
+        stats["dist_stats"] = dist_eval(dataset, val_idx, samples, device, logdir)
     return stats
+
+
+def dist_eval(dataset, val_idx, samples, device, logdir):
+    """``--dist_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
+    tuple), over the internal coordinates of the molecule's bond graph.  Writes ``dist_stats.json``; returns the means
+    (``distributions.summary_of``), or ``None`` when there is nothing to compare (fewer than two hold-out frames, or
+    frames of different molecules)."""
+    from . import distributions
+    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
+        print("--dist_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
+        return None
+    frame = dataset[val_idx[0]]
+    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
+    full = distributions.compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy(), device=device)
+    if logdir:
+        with open(os.path.join(logdir, "dist_stats.json"), "w") as f:
+            json.dump(full, f)
+    return distributions.summary_of(full)
 
 
 def run(params) -> dict:
@@ -315,7 +347,9 @@ def run(params) -> dict:
     if rank == 0 and logdir:
         os.makedirs(logdir, exist_ok=True)
         with open(os.path.join(logdir, "modelparams.json"), "w") as f:
-            json.dump({**params, "mapping": torch.as_tensor(mapping).tolist()}, f, indent=4)
+            # (a flag that is off leaves the file as it was before the flag existed)
+            json.dump({**{k: v for k, v in params.items() if k != "dist_eval" or v}, "mapping": torch.as_tensor(mapping).tolist()},
+                      f, indent=4)
     log_rows, failed = [], False
     columns = ["epoch", "lr", "train_loss", "val_loss", "train_recon", "val_recon", "train_KL", "val_KL",
                "train_graph", "val_graph"]
@@ -394,7 +428,8 @@ def run(params) -> dict:
         test_stats = evaluate_run(params, model, dataset, train_idx, val_idx, device, log_rows[-1] if log_rows else None, logdir)
     if world > 1:
         torch.distributed.destroy_process_group()
-    return {"epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
+    dist = {"dist_stats": test_stats.pop("dist_stats", None) if test_stats else None} if params.get("dist_eval") else {}
+    return {**dist, "epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
             "graph_replays": trainer.replays, "test_stats": test_stats,
             **({"cg_mapping": {k: map_info[k] for k in ("method", "steps", "seconds", "attempts", "loss_recon", "loss_reg")}}
@@ -402,7 +437,9 @@ def run(params) -> dict:
 
 
 def main(argv=None):
-    params = vars(build_parser().parse_args(argv))
+    extras, rest = build_extras_parser().parse_known_args(argv)
+    params = vars(build_parser().parse_args(rest))
+    params.update(vars(extras))
     params["savemodel"] = True                                            # run_ala.py:464
     summary = run(params)
     if int(os.environ.get("RANK", "0")) == 0:

@@ -968,6 +968,49 @@ int cgv_ensemble_check(const float* gen_xyz, const int32_t* frame_ptr /*[n_frame
                        int max_frame_atoms, int n_bonds, int32_t* counts /*[n_frames*n_samples,4]*/,
                        double* pair_sums /*[n_frames*n_samples*n_samples,2]*/, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K15  internal-coordinate histograms -- the numbers behind the reference's offline distribution plots
+ * (CoarseGrainingVAE/plots.py: ramachandran_plot, get_bonds, through mdtraj / pyemma): does an ensemble reproduce the
+ * distribution of the data?  Per feature a histogram over all structures, per pair of torsions a joint histogram (the
+ * Ramachandran map); no [n_structures, features] tensor exists.
+ *   xyz    [n_structures,n_atoms,3]   structures of ONE molecule (fp32; widened on use, all arithmetic below is fp64)
+ *   feat   [n_features,4] int32       atom ids p0..p3 of each feature (the first `kind` of them are read)
+ *   kind   [n_features]   int32       2  bond length  |p0 - p1|
+ *                                     3  angle at p1  atan2(|u x v|, u . v),  u = p0 - p1, v = p2 - p1
+ *                                     4  proper torsion, mdtraj's sign:  atan2(|b2| * b1 . (b2 x b3), (b1 x b2) . (b2 x b3)),
+ *                                        b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2
+ *   pairs  [n_pairs,2]    int32       (f, g): two torsion features whose joint histogram is wanted; may be NULL when
+ *                                     n_pairs == 0.  A pair that names anything but two torsions counts nothing.
+ * Outputs -- ZEROED BY THE CALLER, the launch ADDS (so launches over chunks of structures accumulate):
+ *   counts      [n_features, n_bins + 3] int32   slots: under, n_bins bins, over, invalid
+ *   pair_counts [n_pairs, n_bins2, n_bins2] int32   [p, bin of f, bin of g]
+ * Binning: bin = floor((x - lo) * n_bins / (hi - lo)).
+ *   bonds     [bond_lo, bond_hi): x < lo counts in under, x >= hi in over
+ *   angles    [0, pi]: x == pi counts in the last bin; no under / over
+ *   torsions  [-pi, pi) periodic: x == pi counts in bin 0; no under / over
+ *   invalid   the feature touches a non-finite coordinate (or names an atom outside [0, n_atoms), or has an unknown
+ *             kind): counted in `invalid` and in no pair
+ * Exact integers, independent of the order of the launch's blocks and the same bits on every run (LDS integer atomics
+ * per block, integer vector atomics of the non-zero slots into the outputs).  One launch: a block owns a tile of
+ * cgv_internal_hist_feature_tile(n_bins) features or cgv_internal_hist_pair_tile(n_bins2) pairs and a range of
+ * structures, whose coordinates it stages in LDS; structures of more than cgv_internal_hist_max_staged_atoms() atoms are
+ * gathered from global memory by a second instance of the kernel (same results).
+ * Limits: n_features <= cgv_internal_hist_max_features(), n_pairs <= .._max_pairs(), 1 <= n_bins <= .._max_bins(),
+ * 1 <= n_bins2 <= .._max_bins2() (when n_pairs > 0), n_atoms <= .._max_atoms(); beyond a limit the call fails
+ * (CGV_E_BADARG, cgv_last_error_string) before anything is written -- nothing is clamped or truncated. */
+int cgv_internal_hist_max_features(void);
+int cgv_internal_hist_max_pairs(void);
+int cgv_internal_hist_max_bins(void);
+int cgv_internal_hist_max_bins2(void);
+int cgv_internal_hist_max_atoms(void);
+int cgv_internal_hist_max_staged_atoms(void);
+int cgv_internal_hist_feature_tile(int n_bins);   /* 0 outside the limits */
+int cgv_internal_hist_pair_tile(int n_bins2);     /* 0 outside the limits */
+int cgv_internal_hist(const float* xyz, const int32_t* feat /*[n_features,4]*/, const int32_t* kind /*[n_features]*/,
+                      const int32_t* pairs /*[n_pairs,2]*/, int n_structures, int n_atoms, int n_features, int n_pairs,
+                      int n_bins, int n_bins2, double bond_lo, double bond_hi, int32_t* counts /*[n_features,n_bins+3]*/,
+                      int32_t* pair_counts /*[n_pairs,n_bins2,n_bins2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
