@@ -210,6 +210,14 @@ PROTOTYPES = {
     "cgv_internal_hist_feature_tile": (_i, [_i]),
     "cgv_internal_hist_pair_tile": (_i, [_i]),
     "cgv_internal_hist": (_i, [_p] * 4 + [_i] * 6 + [C.c_double] * 2 + [_p] * 3),
+    "cgv_tica_max_features": (_i, []),
+    "cgv_tica_max_atoms": (_i, []),
+    "cgv_tica_max_bins2": (_i, []),
+    "cgv_tica_max_components": (_i, []),
+    "cgv_tica_moments_splits": (_i, [_i, _i, _i]),
+    "cgv_tica_moments_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_tica_moments": (_i, [_p, _p, _i, _i, _i, _i] + [_p] * 5 + [_p, _sz, _p]),
+    "cgv_tica_project": (_i, [_p] * 4 + [_i] * 4 + [_p, _i, _i, _i] + [C.c_double] * 4 + [_p] * 3),
     "cgv_cgae_resident_fits": (_i, [_i, _i, _i]),
     "cgv_cgae_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cgv_cgae_steps": (_i, [_i] + [_p] * 7 + [_i, _p, C.c_int64, _i, _i, _i, _i, C.c_int64, _i, _f] + [C.c_double] * 4 +

@@ -15,7 +15,7 @@ launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No a
 
     python -m coarsegrainingvae_amd.backmap -model LOGDIR (-cg cg.npz | -traj atoms.npz) [-top top.npz] -n_samples K
         -out out.npz [-frames_per_launch M] [-seed S] [--pair_rmsd] [--require_valid all|heavy -max_rounds R]
-        [--dist_stats [-ref atoms.npz]]
+        [--dist_stats [-ref atoms.npz]] [--tica_stats [-tica_lag 100] [-tica_bins 50]]
 
 ``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
 the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
@@ -29,6 +29,13 @@ extra_all, missing_heavy, extra_heavy), with ``--pair_rmsd`` ``pair_rmsd_all`` /
 all ``T * K`` of them against the frames of ``-ref`` (a ``tools/traj_to_npz.py`` file with the topology's atom order;
 default: the frames of ``-traj``): per-feature and per-(phi, psi) Jensen-Shannon divergences with their noise floor go to
 ``dist_stats.json`` next to ``-out``, their means into the summary line under ``"dist_stats"``.  Needs a topology.
+
+``--tica_stats``: do they populate the slow, collective states of the simulation?  ``tica.compare``: TICA (lag
+``-tica_lag`` frames) of the backbone distances is fitted on the frames of ``-ref`` (default: those of ``-traj``; a
+``traj_starts`` key of the file cuts them into segments) taken as a time-ordered trajectory, the generated structures are
+projected on its two slowest components and the maps compared over ``-tica_bins`` x ``-tica_bins`` bins.  Everything goes
+to ``tica_stats.json`` next to ``-out``, the short form into the summary line under ``"tica_stats"``.  Needs a topology
+with a peptide backbone and at least ``lag + 2`` reference frames.
 """
 from __future__ import annotations
 
@@ -274,6 +281,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dist_stats", action="store_true", default=False,
                    help="compare the internal-coordinate distributions of the output with -ref; writes dist_stats.json next to -out")
     p.add_argument("-ref", type=str, default=None, help="all-atom tools/traj_to_npz.py file, same atom order (default: the frames of -traj)")
+    p.add_argument("--tica_stats", action="store_true", default=False,
+                   help="compare the output with -ref in the plane of the reference's two slowest independent components; "
+                        "writes tica_stats.json next to -out")
+    p.add_argument("-tica_lag", type=int, default=100, help="lag of --tica_stats in frames of the reference")
+    p.add_argument("-tica_bins", type=int, default=50, help="bins per component of --tica_stats")
     return p
 
 
@@ -293,19 +305,20 @@ def read_inputs(args, params, device=None) -> dict:
     mapping = np.asarray(params["mapping"], dtype=np.int64)
     n, N = mapping.shape[0], int(mapping.max()) + 1
     z = bonds = ref_xyz = None
-    dist_stats = getattr(args, "dist_stats", False)
-    if getattr(args, "ref", None) and not dist_stats:
-        raise SystemExit("-ref is the reference of --dist_stats")
+    dist_stats, tica_stats = getattr(args, "dist_stats", False), getattr(args, "tica_stats", False)
+    need_ref, starts = dist_stats or tica_stats, None
+    if getattr(args, "ref", None) and not need_ref:
+        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats")
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
         f = _npz(args.traj, ["xyz", "z", "bonds"])
-        xyz, z, bonds = np.asarray(f["xyz"], dtype=np.float32), f["z"], f["bonds"]
+        xyz, z, bonds, starts = np.asarray(f["xyz"], dtype=np.float32), f["z"], f["bonds"], f.get("traj_starts")
         if xyz.ndim != 3 or xyz.shape[1:] != (n, 3):
             raise SystemExit(f"{args.traj}: xyz is {xyz.shape}, the run's mapping has {n} atoms")
         from .ops import scatter_mean
         T = xyz.shape[0]
-        ref_xyz = xyz if dist_stats else None
+        ref_xyz = xyz if need_ref else None
         index = (torch.from_numpy(mapping).to(device)[None, :] + N * torch.arange(T, device=device)[:, None]).reshape(-1)
         cg = scatter_mean(torch.from_numpy(xyz).to(device).reshape(T * n, 3).contiguous(), index, dim=0,
                           dim_size=T * N).reshape(T, N, 3).cpu().numpy()
@@ -322,21 +335,34 @@ def read_inputs(args, params, device=None) -> dict:
         bonds = canonical_bonds(bonds)
     if args.require_valid and bonds is None:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
-    if dist_stats:
+    if need_ref:
+        switch = "--dist_stats" if dist_stats else "--tica_stats"
         if bonds is None:
-            raise SystemExit("--dist_stats needs a topology (-top, or the z / bonds of -traj)")
+            raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
             f = _npz(args.ref, ["xyz", "z"])
-            ref_xyz = np.asarray(f["xyz"], dtype=np.float32)
+            ref_xyz, starts = np.asarray(f["xyz"], dtype=np.float32), f.get("traj_starts")
             if ref_xyz.ndim != 3 or ref_xyz.shape[1:] != (n, 3):
                 raise SystemExit(f"{args.ref}: xyz is {ref_xyz.shape}, the topology has {n} atoms")
             if not np.array_equal(np.asarray(f["z"]).astype(np.int64).reshape(-1), np.asarray(z).astype(np.int64).reshape(-1)):
                 raise SystemExit(f"{args.ref}: z differs from the topology's (the reference must list the same atoms in the same order)")
         if ref_xyz is None or ref_xyz.shape[0] < 2:
-            raise SystemExit("--dist_stats needs reference frames: -ref file.npz (or -traj as the source), at least two")
+            raise SystemExit(f"{switch} needs reference frames: -ref file.npz (or -traj as the source), at least two")
+        if tica_stats:
+            from . import tica
+            if args.tica_lag < 1 or ref_xyz.shape[0] < args.tica_lag + 2:
+                raise SystemExit(f"--tica_stats needs 1 <= -tica_lag and at least lag + 2 reference frames: {ref_xyz.shape[0]} "
+                                 f"frames, lag {args.tica_lag}")
+            if tica.backbone_atoms(z, bonds).shape[0] == 0:
+                raise SystemExit("--tica_stats: the topology has no peptide backbone to take the distances from")
+            try:
+                tica.split_segments(ref_xyz, starts)
+            except ValueError as err:
+                raise SystemExit(f"--tica_stats: {err}")
     if params.get("cg_radius_graph") and bonds is None:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
-    return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if dist_stats else {})}
+    return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if need_ref else {}),
+            **({"ref_starts": starts} if tica_stats else {})}
 
 
 def run(args) -> dict:
@@ -386,6 +412,13 @@ def run(args) -> dict:
         with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "dist_stats.json"), "w") as f:
             json.dump(stats, f)
         dist = {"dist_stats": distributions.summary_of(stats)}
+    if args.tica_stats:
+        from . import tica
+        stats = tica.compare(tica.split_segments(inp["ref_xyz"], inp["ref_starts"]), res["xyz"].reshape(T * K, -1, 3), z, bonds,
+                             lag=args.tica_lag, n_bins2=args.tica_bins, device=device)
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "tica_stats.json"), "w") as f:
+            json.dump(stats, f)
+        dist["tica_stats"] = tica.summary_of(stats)
 
     def mean(key):
         if key not in res:

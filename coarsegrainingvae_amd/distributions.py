@@ -102,8 +102,22 @@ def peptide_backbone_torsions(z, bonds):
     ``psi`` are lists of atom 4-tuples, ``pairs`` lists ``(index into phi, index into psi)`` of the residues that have
     both.  Nothing matches (a hydrocarbon): three empty lists."""
     z = np.asarray(z).astype(np.int64).reshape(-1)
+    nbrs = _adjacency(z.shape[0], bonds)
+    is_amide, residues = _peptide_residues(z, nbrs)
+    phi, psi, pairs = [], [], []
+    for N, CA, C in residues:
+        mine_phi = [(Cp, N, CA, C) for Cp in nbrs[N] if is_amide[Cp] and Cp not in (C, CA)]
+        mine_psi = [(N, CA, C, Np) for Np in nbrs[C] if z[Np] == 7 and Np not in (N, CA)]
+        pairs += [(len(phi) + a, len(psi) + b) for a in range(len(mine_phi)) for b in range(len(mine_psi))]
+        phi += mine_phi
+        psi += mine_psi
+    return phi, psi, pairs
+
+
+def _peptide_residues(z, nbrs):
+    """The rule of ``peptide_backbone_torsions``: ``(is_amide [n], [(N, CA, C), ...])`` in the order of N, then of its
+    neighbours CA, then of CA's neighbours C (``tica.backbone_atoms`` selects the same atoms)."""
     n = z.shape[0]
-    nbrs = _adjacency(n, bonds)
 
     def amide(c):
         if z[c] != 6:
@@ -111,22 +125,15 @@ def peptide_backbone_torsions(z, bonds):
         carbonyl = [o for o in nbrs[c] if z[o] == 8 and len(nbrs[o]) == 1]
         return len(carbonyl) == 1 and any(z[a] == 7 for a in nbrs[c])
     is_amide = [amide(c) for c in range(n)]
-    phi, psi, pairs = [], [], []
+    residues = []
     for N in range(n):
         if z[N] != 7:
             continue
         for CA in nbrs[N]:
             if z[CA] != 6 or is_amide[CA]:
                 continue
-            for C in nbrs[CA]:
-                if not is_amide[C] or C == N:
-                    continue
-                mine_phi = [(Cp, N, CA, C) for Cp in nbrs[N] if is_amide[Cp] and Cp not in (C, CA)]
-                mine_psi = [(N, CA, C, Np) for Np in nbrs[C] if z[Np] == 7 and Np not in (N, CA)]
-                pairs += [(len(phi) + a, len(psi) + b) for a in range(len(mine_phi)) for b in range(len(mine_psi))]
-                phi += mine_phi
-                psi += mine_psi
-    return phi, psi, pairs
+            residues += [(N, CA, C) for C in nbrs[CA] if is_amide[C] and C != N]
+    return is_amide, residues
 
 
 def backbone_pairs(coords: InternalCoords, z, bonds) -> Tuple[InternalCoords, List[Tuple[int, int]]]:

@@ -108,6 +108,10 @@ def build_extras_parser() -> argparse.ArgumentParser:
     p.add_argument("--dist_eval", action="store_true", default=False,
                    help="after the evaluation, compare the internal-coordinate distributions of the hold-out frames with "
                         "their prior samples (distributions.compare): dist_stats.json in the log directory")
+    p.add_argument("--tica_eval", action="store_true", default=False,
+                   help="after the evaluation, fit TICA on the -traj file's frames in file order and compare the hold-out "
+                        "samples with them in the plane of its two slowest components (tica.compare): tica_stats.json")
+    p.add_argument("-tica_lag", type=int, default=100, help="lag of --tica_eval in frames of the file")
     return p
 
 
@@ -273,6 +277,8 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
                                 cg_xyzs=samples[2], recon_xyzs=samples[3], n_ensemble=params["n_ensemble"])
     if params.get("dist_eval"):
         stats["dist_stats"] = dist_eval(dataset, val_idx, samples, device, logdir)
+    if params.get("tica_eval"):
+        stats["tica_stats"] = tica_eval(params, dataset, val_idx, samples, device, logdir)
     return stats
 
 
@@ -292,6 +298,36 @@ def dist_eval(dataset, val_idx, samples, device, logdir):
         with open(os.path.join(logdir, "dist_stats.json"), "w") as f:
             json.dump(full, f)
     return distributions.summary_of(full)
+
+
+def tica_eval(params, dataset, val_idx, samples, device, logdir):
+    """``--tica_eval``: TICA fitted on the frames of the ``-traj`` file IN FILE ORDER (the training order may be shuffled;
+    a ``traj_starts`` key cuts the file into segments), the hold-out samples (``samples``: ``evaluate.sample_ensemble``'s
+    tuple) compared with them.  Writes ``tica_stats.json``; returns ``tica.summary_of``, or ``None`` when there is
+    nothing to compare: synthetic frames have no time order, the file is shorter than ``lag + 2`` frames, or the
+    molecule has no peptide backbone."""
+    from . import tica
+    lag = int(params.get("tica_lag", 100))
+    if not params.get("traj"):
+        print("--tica_eval skipped: synthetic frames have no time order (it needs -traj)", file=sys.stderr, flush=True)
+        return None
+    if samples is None or not isinstance(samples[0], np.ndarray):
+        print("--tica_eval skipped: there are no hold-out samples", file=sys.stderr, flush=True)
+        return None
+    with np.load(params["traj"]) as f:
+        xyz, z, bonds = np.asarray(f["xyz"], dtype=np.float32)[: params["ndata"]], f["z"], f["bonds"]
+        starts = f["traj_starts"] if "traj_starts" in f.files else None
+    if starts is not None:
+        starts = np.asarray(starts)[np.asarray(starts) < xyz.shape[0]]
+    if lag < 1 or xyz.shape[0] < lag + 2 or tica.backbone_atoms(z, bonds).shape[0] == 0:
+        print(f"--tica_eval skipped: it needs a peptide backbone and at least lag + 2 = {lag + 2} frames in file order",
+              file=sys.stderr, flush=True)
+        return None
+    full = tica.compare(tica.split_segments(xyz, starts), samples[0].reshape(-1, xyz.shape[1], 3), z, bonds, lag=lag, device=device)
+    if logdir:
+        with open(os.path.join(logdir, "tica_stats.json"), "w") as f:
+            json.dump(full, f)
+    return tica.summary_of(full)
 
 
 def run(params) -> dict:
@@ -348,7 +384,9 @@ def run(params) -> dict:
         os.makedirs(logdir, exist_ok=True)
         with open(os.path.join(logdir, "modelparams.json"), "w") as f:
             # (a flag that is off leaves the file as it was before the flag existed)
-            json.dump({**{k: v for k, v in params.items() if k != "dist_eval" or v}, "mapping": torch.as_tensor(mapping).tolist()},
+            off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"))
+                   if not params.get(switch)]
+            json.dump({**{k: v for k, v in params.items() if k not in off}, "mapping": torch.as_tensor(mapping).tolist()},
                       f, indent=4)
     log_rows, failed = [], False
     columns = ["epoch", "lr", "train_loss", "val_loss", "train_recon", "val_recon", "train_KL", "val_KL",
@@ -429,6 +467,8 @@ def run(params) -> dict:
     if world > 1:
         torch.distributed.destroy_process_group()
     dist = {"dist_stats": test_stats.pop("dist_stats", None) if test_stats else None} if params.get("dist_eval") else {}
+    if params.get("tica_eval"):
+        dist["tica_stats"] = test_stats.pop("tica_stats", None) if test_stats else None
     return {**dist, "epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
             "graph_replays": trainer.replays, "test_stats": test_stats,

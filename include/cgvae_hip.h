@@ -1011,6 +1011,54 @@ int cgv_internal_hist(const float* xyz, const int32_t* feat /*[n_features,4]*/, 
                       int n_bins, int n_bins2, double bond_lo, double bond_hi, int32_t* counts /*[n_features,n_bins+3]*/,
                       int32_t* pair_counts /*[n_pairs,n_bins2,n_bins2]*/, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K16  time-lagged independent component analysis (TICA) -- does an ensemble populate the slow, collective states of the
+ * simulation?  Replaces what the reference does offline through pyemma (CoarseGrainingVAE/postanalysis.py:25-68:
+ * pairwise backbone distances, tica(lag=100) on the simulation, tica.transform of the generated structures).
+ *   pairs  [d,2] int32    atom pairs (I, J); feature f of a frame is the distance of its pair, computed in fp32 as
+ *                         sqrt((dx*dx + dy*dy) + dz*dz), every operation rounded on its own (no FMA contraction), the
+ *                         square root correctly rounded, then widened to fp64.  An index outside [0, n_atoms) reads
+ *                         atom 0 (the host wrapper refuses such tables); nothing is read out of bounds.
+ * No [frames, d] feature tensor exists in memory.
+ *
+ * cgv_tica_moments: xyz [n_frames,n_atoms,3] is ONE contiguous, time-ordered segment.  With x_t = f(t), y_t = f(t + lag)
+ * over t in [0, n_frames - lag) the call ADDS to the caller's fp64 buffers (zeroed by the caller before the first call)
+ *   sum_x [d] += sum x_t   sum_y [d] += sum y_t   cxx [d,d] += sum x_t x_t^T   cyy [d,d] += sum y_t y_t^T
+ *   cxy [d,d] += sum x_t y_t^T
+ * n_frames <= lag adds nothing and returns 0.  Non-finite coordinates propagate into the sums.
+ * Two launches: grid (tile pairs bi <= bj of 32 features, cgv_tica_moments_splits() frame ranges) x 256 threads, a
+ * block stages 16 frame pairs of its tiles' features in LDS as fp64 and accumulates X_i X_j^T, Y_i Y_j^T, X_i Y_j^T and
+ * X_j Y_i^T in registers with v_mfma_f64_16x16x4_f64, then writes its tiles to its range's slice of the workspace;
+ * the second launch sums the ranges in ascending order into the totals and fills cxx / cyy below the diagonal from above
+ * it.  No floating-point atomics: the same bits on every run, cxx and cyy exactly symmetric.
+ * workspace: cgv_tica_moments_workspace_bytes(n_frames, d, lag) bytes, 8-byte aligned, contents need not survive.
+ * Limits: 1 <= lag, d <= cgv_tica_max_features(), n_atoms <= cgv_tica_max_atoms(); beyond a limit the call fails
+ * (CGV_E_BADARG) before any launch.  Bound: see DESIGN.md (K16 row).
+ *
+ * cgv_tica_project: structures xyz [n_structures,n_atoms,3] onto a fitted model, mean [d], W [d,k] fp64,
+ * 1 <= k <= cgv_tica_max_components() (8).  One launch, one wave per structure.
+ *   ics [n_structures,k] fp64 (may be NULL)   ics[s,c] = sum_f (f_s[f] - mean[f]) * W[f,c]: each lane sums features
+ *                         lane, lane + 64, .. in ascending order, a fixed tree combines the lanes (same bits every run)
+ *   counts [n_bins2,n_bins2] int32, outside [1] int32 (both or neither; ZEROED BY THE CALLER, the launch ADDS)
+ *                         the joint histogram of components (comp_a, comp_b): bin = floor((v - lo) * n_bins2 / (hi - lo))
+ *                         in fp64 for lo <= v < hi, counts[bin_a, bin_b]; a structure with either component outside its
+ *                         range or non-finite counts once in outside.  LDS integer atomics, one integer vector atomic
+ *                         per non-zero slot: exact in any order.
+ * Limits as above, 1 <= n_bins2 <= cgv_tica_max_bins2(), lo < hi finite. */
+int cgv_tica_max_features(void);
+int cgv_tica_max_atoms(void);
+int cgv_tica_max_bins2(void);
+int cgv_tica_max_components(void);
+int cgv_tica_moments_splits(int n_frames, int d, int lag);            /* frame ranges of a call; 0: the call adds nothing */
+size_t cgv_tica_moments_workspace_bytes(int n_frames, int d, int lag);
+int cgv_tica_moments(const float* xyz, const int32_t* pairs /*[d,2]*/, int n_frames, int n_atoms, int d, int lag,
+                     double* sum_x, double* sum_y, double* cxx, double* cyy, double* cxy, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int cgv_tica_project(const float* xyz, const int32_t* pairs /*[d,2]*/, const double* mean, const double* W /*[d,k]*/,
+                     int n_structures, int n_atoms, int d, int k, double* ics /*[n_structures,k]*/, int comp_a, int comp_b,
+                     int n_bins2, double lo_a, double hi_a, double lo_b, double hi_b, int32_t* counts, int32_t* outside,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ dependencies here.  This tool turns what a user has into the one small format th
               z    int64   [n]        atomic numbers    (datasets.py get_atomNum)
               bonds int64  [Eb, 2]    bond graph        (datasets.py:470-472: traj.top bonds)
               mapping int64 [n]       optional atom -> bead map (datasets.py:252-330 learn / build it; here: given or absent)
+              traj_starts int64 [m]   optional (--traj-starts): first frame of every independent trajectory in the file,
+                                      ascending, the first 0; only the TICA analysis (tica.split_segments) reads it
 
 Inputs:
     multi-frame .xyz text        python tools/traj_to_npz.py traj.xyz out.npz [--bonds bonds.txt] [--mapping map.txt]
@@ -59,6 +61,7 @@ def main(argv=None):
     ap.add_argument("--z", help="text file: one atomic number per line (array inputs)")
     ap.add_argument("--bonds", help="text file: two atom indices per line")
     ap.add_argument("--mapping", help="text file: one bead index per atom")
+    ap.add_argument("--traj-starts", help="text file: the first frame (after --stride / --max-frames) of every independent trajectory")
     ap.add_argument("--stride", type=int, default=1)
     ap.add_argument("--max-frames", type=int, default=None)
     a = ap.parse_args(argv)
@@ -95,6 +98,11 @@ def main(argv=None):
         out["mapping"] = np.loadtxt(a.mapping, dtype=np.int64).reshape(-1)
         if out["mapping"].shape[0] != z.shape[0]:
             raise SystemExit("mapping length differs from the number of atoms")
+    if a.traj_starts:
+        starts = np.loadtxt(a.traj_starts, dtype=np.int64).reshape(-1)
+        if starts.shape[0] == 0 or starts[0] != 0 or (np.diff(starts) <= 0).any() or starts[-1] >= xyz.shape[0]:
+            raise SystemExit("--traj-starts: ascending frame indices, the first 0, all below the number of frames")
+        out["traj_starts"] = starts
     np.savez_compressed(a.out, **out)
     print(f"{a.out}: {xyz.shape[0]} frames x {xyz.shape[1]} atoms, {bonds.shape[0]} bonds"
           + (f", {int(out['mapping'].max()) + 1} beads" if "mapping" in out else ""))
