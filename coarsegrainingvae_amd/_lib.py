@@ -218,6 +218,10 @@ PROTOTYPES = {
     "cgv_tica_moments_workspace_bytes": (_sz, [_i, _i, _i]),
     "cgv_tica_moments": (_i, [_p, _p, _i, _i, _i, _i] + [_p] * 5 + [_p, _sz, _p]),
     "cgv_tica_project": (_i, [_p] * 4 + [_i] * 4 + [_p, _i, _i, _i] + [C.c_double] * 4 + [_p] * 3),
+    "cgv_superpose_max_structures": (_i, []),
+    "cgv_superpose_max_atoms": (_i, []),
+    "cgv_superpose_workspace_bytes": (_sz, [_i, _i]),
+    "cgv_superpose": (_i, [_p, _p, _p] + [_i] * 7 + [_p] * 5 + [_p, _sz, _p]),
     "cgv_cgae_resident_fits": (_i, [_i, _i, _i]),
     "cgv_cgae_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cgv_cgae_steps": (_i, [_i] + [_p] * 7 + [_i, _p, C.c_int64, _i, _i, _i, _i, C.c_int64, _i, _f] + [C.c_double] * 4 +

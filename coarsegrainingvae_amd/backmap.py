@@ -16,6 +16,7 @@ launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No a
     python -m coarsegrainingvae_amd.backmap -model LOGDIR (-cg cg.npz | -traj atoms.npz) [-top top.npz] -n_samples K
         -out out.npz [-frames_per_launch M] [-seed S] [--pair_rmsd] [--require_valid all|heavy -max_rounds R]
         [--dist_stats [-ref atoms.npz]] [--tica_stats [-tica_lag 100] [-tica_bins 50]]
+        [--cov_stats [-cov_thresholds 0.5 1.0 2.0] [-cov_atoms heavy]]
 
 ``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
 the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
@@ -36,6 +37,12 @@ default: the frames of ``-traj``): per-feature and per-(phi, psi) Jensen-Shannon
 projected on its two slowest components and the maps compared over ``-tica_bins`` x ``-tica_bins`` bins.  Everything goes
 to ``tica_stats.json`` next to ``-out``, the short form into the summary line under ``"tica_stats"``.  Needs a topology
 with a peptide backbone and at least ``lag + 2`` reference frames.
+
+``--cov_stats``: does every reference frame have a backmapped structure near it, and is every backmapped structure near
+some reference frame?  ``coverage.compare``: superposed RMSD (K17) between all ``T * K`` structures and the frames of
+``-ref`` (default: those of ``-traj``) over the ``-cov_atoms`` (``heavy`` or ``all``): COV-R / MAT-R, COV-P / MAT-P at the
+``-cov_thresholds`` (Angstrom), with the even / odd floor of the reference, go to ``cov_stats.json`` next to ``-out``, the
+short form into the summary line under ``"cov_stats"``.  Needs a topology (for the elements).
 """
 from __future__ import annotations
 
@@ -286,6 +293,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "writes tica_stats.json next to -out")
     p.add_argument("-tica_lag", type=int, default=100, help="lag of --tica_stats in frames of the reference")
     p.add_argument("-tica_bins", type=int, default=50, help="bins per component of --tica_stats")
+    p.add_argument("--cov_stats", action="store_true", default=False,
+                   help="coverage and precision of the output against -ref by superposed RMSD; writes cov_stats.json next to -out")
+    p.add_argument("-cov_thresholds", type=float, nargs="+", default=[0.5, 1.0, 2.0], help="RMSD thresholds of --cov_stats in Angstrom")
+    p.add_argument("-cov_atoms", choices=("heavy", "all"), default="heavy", help="atoms that --cov_stats superposes")
     return p
 
 
@@ -306,9 +317,10 @@ def read_inputs(args, params, device=None) -> dict:
     n, N = mapping.shape[0], int(mapping.max()) + 1
     z = bonds = ref_xyz = None
     dist_stats, tica_stats = getattr(args, "dist_stats", False), getattr(args, "tica_stats", False)
-    need_ref, starts = dist_stats or tica_stats, None
+    cov_stats = getattr(args, "cov_stats", False)
+    need_ref, starts = dist_stats or tica_stats or cov_stats, None
     if getattr(args, "ref", None) and not need_ref:
-        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats")
+        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats")
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
@@ -336,7 +348,7 @@ def read_inputs(args, params, device=None) -> dict:
     if args.require_valid and bonds is None:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
     if need_ref:
-        switch = "--dist_stats" if dist_stats else "--tica_stats"
+        switch = "--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats"
         if bonds is None:
             raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
@@ -359,6 +371,12 @@ def read_inputs(args, params, device=None) -> dict:
                 tica.split_segments(ref_xyz, starts)
             except ValueError as err:
                 raise SystemExit(f"--tica_stats: {err}")
+        if cov_stats:
+            from . import coverage
+            if not args.cov_thresholds or min(args.cov_thresholds) <= 0:
+                raise SystemExit("--cov_stats: -cov_thresholds must be positive RMSDs in Angstrom")
+            if coverage.select_atoms(z, args.cov_atoms).shape[0] == 0:
+                raise SystemExit(f"--cov_stats: the topology has no {args.cov_atoms} atoms to superpose")
     if params.get("cg_radius_graph") and bonds is None:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
     return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if need_ref else {}),
@@ -419,6 +437,13 @@ def run(args) -> dict:
         with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "tica_stats.json"), "w") as f:
             json.dump(stats, f)
         dist["tica_stats"] = tica.summary_of(stats)
+    if args.cov_stats:
+        from . import coverage
+        stats = coverage.compare(inp["ref_xyz"], res["xyz"].reshape(T * K, -1, 3), z, thresholds=args.cov_thresholds,
+                                 atoms=args.cov_atoms, device=device)
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "cov_stats.json"), "w") as f:
+            json.dump(stats, f)
+        dist["cov_stats"] = coverage.summary_of(stats)
 
     def mean(key):
         if key not in res:

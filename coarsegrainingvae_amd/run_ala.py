@@ -112,7 +112,19 @@ def build_extras_parser() -> argparse.ArgumentParser:
                    help="after the evaluation, fit TICA on the -traj file's frames in file order and compare the hold-out "
                         "samples with them in the plane of its two slowest components (tica.compare): tica_stats.json")
     p.add_argument("-tica_lag", type=int, default=100, help="lag of --tica_eval in frames of the file")
+    p.add_argument("--cov_eval", action="store_true", default=False,
+                   help="after the evaluation, coverage and precision of the hold-out frames' prior samples against those "
+                        "frames by superposed heavy-atom RMSD (coverage.compare): cov_stats.json in the log directory")
     return p
+
+
+def stored_params(params: dict) -> dict:
+    """What ``modelparams.json`` records of the parameters: a switch of ``build_extras_parser`` that is off leaves the
+    file as it was before the switch existed (its key, and the keys of its options, are left out)."""
+    off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"),
+                               ("cov_eval", "cov_eval"))
+           if not params.get(switch)]
+    return {k: v for k, v in params.items() if k not in off}
 
 
 def annotate_job(task, job_name, n_cg):
@@ -279,6 +291,8 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
         stats["dist_stats"] = dist_eval(dataset, val_idx, samples, device, logdir)
     if params.get("tica_eval"):
         stats["tica_stats"] = tica_eval(params, dataset, val_idx, samples, device, logdir)
+    if params.get("cov_eval"):
+        stats["cov_stats"] = cov_eval(dataset, val_idx, samples, device, logdir)
     return stats
 
 
@@ -298,6 +312,25 @@ def dist_eval(dataset, val_idx, samples, device, logdir):
         with open(os.path.join(logdir, "dist_stats.json"), "w") as f:
             json.dump(full, f)
     return distributions.summary_of(full)
+
+
+def cov_eval(dataset, val_idx, samples, device, logdir):
+    """``--cov_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
+    tuple) by superposed heavy-atom RMSD: does every hold-out frame have a sample near it, is every sample near a hold-out
+    frame.  Writes ``cov_stats.json``; returns ``coverage.summary_of``, or ``None`` when there is nothing to compare
+    (fewer than two hold-out frames, or frames of different molecules)."""
+    from . import coverage
+    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
+        print("--cov_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
+        return None
+    frame = dataset[val_idx[0]]
+    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
+    atoms = "heavy" if (z != 1).any() else "all"
+    full = coverage.compare(samples[1], samples[0].reshape(-1, n, 3), z, atoms=atoms, device=device)
+    if logdir:
+        with open(os.path.join(logdir, "cov_stats.json"), "w") as f:
+            json.dump(full, f)
+    return coverage.summary_of(full)
 
 
 def tica_eval(params, dataset, val_idx, samples, device, logdir):
@@ -383,11 +416,7 @@ def run(params) -> dict:
     if rank == 0 and logdir:
         os.makedirs(logdir, exist_ok=True)
         with open(os.path.join(logdir, "modelparams.json"), "w") as f:
-            # (a flag that is off leaves the file as it was before the flag existed)
-            off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"))
-                   if not params.get(switch)]
-            json.dump({**{k: v for k, v in params.items() if k not in off}, "mapping": torch.as_tensor(mapping).tolist()},
-                      f, indent=4)
+            json.dump({**stored_params(params), "mapping": torch.as_tensor(mapping).tolist()}, f, indent=4)
     log_rows, failed = [], False
     columns = ["epoch", "lr", "train_loss", "val_loss", "train_recon", "val_recon", "train_KL", "val_KL",
                "train_graph", "val_graph"]
@@ -469,6 +498,8 @@ def run(params) -> dict:
     dist = {"dist_stats": test_stats.pop("dist_stats", None) if test_stats else None} if params.get("dist_eval") else {}
     if params.get("tica_eval"):
         dist["tica_stats"] = test_stats.pop("tica_stats", None) if test_stats else None
+    if params.get("cov_eval"):
+        dist["cov_stats"] = test_stats.pop("cov_stats", None) if test_stats else None
     return {**dist, "epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
             "graph_replays": trainer.replays, "test_stats": test_stats,

@@ -1059,6 +1059,44 @@ int cgv_tica_project(const float* xyz, const int32_t* pairs /*[d,2]*/, const dou
                      int n_bins2, double lo_a, double hi_a, double lo_b, double hi_b, int32_t* counts, int32_t* outside,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K17  superposed RMSD between two sets of structures -- coverage (recall) and precision of a generated ensemble: does
+ * every conformation of the data have a generated structure near it, is every generated structure near some conformation
+ * of the data?  "Near" is the whole-structure RMSD after optimal superposition.  Nothing in the reference computes it.
+ *   a [sa,n_atoms,3], b [sb,n_atoms,3] fp32   the two sets (the same pointer for a set against itself)
+ *   sel [m] int32, 1 <= m <= n_atoms          the atoms that count.  An index outside [0, n_atoms) reads atom 0 (the host
+ *                                             wrapper refuses such a selection); nothing is read out of bounds.
+ *   rmsd^2(i, j) = max(0, G_a[i] + G_b[j] - 2 lambda(i, j)) / m
+ * G: the sum of squared coordinates over sel after subtracting their centroid (summed over sel in ascending order);
+ * lambda: the largest eigenvalue of the 4 x 4 quaternion key matrix of M = sum_k a~_i[k]^T b~_j[k], i.e. the maximum over
+ * PROPER rotations only -- a mirror image is not a superposition.  Coordinates are widened on load, everything after is
+ * fp64.  lambda comes from a fixed number of cyclic Jacobi sweeps: degenerate M (one or two atoms, collinear or planar
+ * selections, identical structures) is an ordinary input.
+ * A structure with a non-finite coordinate inside sel is `bad`: its pairs are NaN in `dense` and enter no minimum.
+ *
+ * The call MERGES into the caller's running nearest neighbours (initialised by the caller to +inf / -1):
+ *   row_min [sa] fp64, row_arg [sa] int32     min over j of rmsd^2(i, j) and the GLOBAL index off_b + j of that column
+ *   col_min [sb] fp64, col_arg [sb] int32     min over i and off_a + i
+ * keeping the smaller value and, on equal bits, the lower index -- so a caller may cut both sets into chunks, pass each
+ * pair of chunks with its offsets, and get the bits of a single call.  same != 0 skips the pairs off_a + i == off_b + j
+ * (a set against itself).
+ *   dense [sa,sb] fp64 (may be NULL)          every rmsd^2 of this call, overwritten (the diagonal of `same` included)
+ * Launches: one thread per structure for centroid, G and bad; grid (tiles of 32 rows, tiles of 32 columns) x 256 threads,
+ * a block stages 16 selected atoms of its 64 structures as three fp64 coordinate planes per side in LDS, each wave keeps
+ * the nine entries of M for its 16 x 16 pairs as nine accumulators of v_mfma_f64_16x16x4_f64, solves for lambda in
+ * registers and the block reduces its 32 x 32 values to per-row and per-column (value, index) partials in the workspace;
+ * a last launch merges the partials in ascending tile order.  No [sa,sb] tensor unless `dense` is asked for, no
+ * floating-point atomics: the same bits on every run.
+ * workspace: cgv_superpose_workspace_bytes(sa, sb) bytes, 8-byte aligned, contents need not survive.
+ * Limits: sa, sb <= cgv_superpose_max_structures(), n_atoms <= cgv_superpose_max_atoms(), off + s <= INT32_MAX; beyond a
+ * limit the call fails (CGV_E_BADARG) before any launch.  Bound: see DESIGN.md (K17 row). */
+int cgv_superpose_max_structures(void);
+int cgv_superpose_max_atoms(void);
+size_t cgv_superpose_workspace_bytes(int sa, int sb);
+int cgv_superpose(const float* a, const float* b, const int32_t* sel /*[m]*/, int sa, int sb, int n_atoms, int m, int off_a,
+                  int off_b, int same, double* row_min, int32_t* row_arg, double* col_min, int32_t* col_arg,
+                  double* dense /*[sa,sb] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
