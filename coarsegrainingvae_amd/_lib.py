@@ -227,6 +227,12 @@ PROTOTYPES = {
     "cgv_cgae_steps": (_i, [_i] + [_p] * 7 + [_i, _p, C.c_int64, _i, _i, _i, _i, C.c_int64, _i, _f] + [C.c_double] * 4 +
                        [C.c_uint64, _p, _p, _p, _p, _sz, _p]),
     "cgv_cgae_noise": (_i, [C.c_uint64, C.c_int64, _i, _i, _i, _p, _p]),
+    "cgv_newman_resident_fits": (_i, [_i, _i]),
+    "cgv_newman_groups": (_i, [_i, _i]),
+    "cgv_newman_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "cgv_newman_betweenness": (_i, [_p] * 4 + [_i] * 4 + [_p, _p, _sz, _p]),
+    "cgv_newman_components": (_i, [_p] * 5 + [_i] * 4 + [_p, _p, _p, _sz, _p]),
+    "cgv_newman_partition": (_i, [_p] * 8 + [_i] * 6 + [_p, _sz, _p]),
 }
 
 

@@ -34,6 +34,7 @@ HOST = {
     "update_fused_bwd": 1,  # UpdateBlock backward on more than 32 bead rows: 1 the norm / stack backward in the store epilogue of s_dense.0's backward-input product (cgv_tile_linear_bwd_input_norm_stack: one launch less per layer), 0 product + element-wise launch
     "strip_split": 1,       # weight gradients of layers with 32 .. 96 operand rows (bead-level layers of a large bead batch, gathered rows of 4 - 8 ranks): 1 from 64 rows on strips on the bf16 matrix path with split operands (x split once per problem, g once per strip), 0 fp32 MFMA strips, 2 split strips at every row count (tests)
     "cgae_form": 0,         # mapping learner (cgmap.py): 0 rule of cgv_cgae_resident_fits (state in one workgroup's LDS when n_atoms x n_cgs fits), 1 resident, 2 streamed (tests force either at a small size)
+    "newman_form": 0,       # Girvan-Newman partition (cgmap.partition_newman): 0 rule of cgv_newman_resident_fits (a workgroup's per-source state in LDS when n_atoms / n_edges fit), 1 resident, 2 streamed (tests force either at a small size)
     "decoder_dense": 0,     # full-width products of the fused decoder loop: 0 four-column blocks (cgv_decoder_dense_fwd), 1 skinny_fwd_k
 }
 _DEFAULTS = dict(HOST)

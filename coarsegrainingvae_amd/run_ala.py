@@ -4,9 +4,10 @@ MI355X hot path.  Every flag keeps its name, type and default.  What is in scope
 training loop of one fold: model wiring (run_ala.py:184-209), Adam + ReduceLROnPlateau +
 early stopping (211-215, 232-284) and the CSV log columns (228-229, 252-258).
 
-Out of scope: trajectory download / mdtraj loading, the graph-partition
-CG mappings (newman, backbonepartition), k-fold cross-validation.  ``-cg_method cgae`` on a ``-traj`` file without a
-``mapping`` learns the atom -> bead map on the device first (cgmap.py, datasets.py:190-249, 303-312).  Frames come either from ``--synthetic`` (uniform random
+Out of scope: trajectory download / mdtraj loading, the ``minimal`` / ``alpha`` mappings
+(they need atom names), k-fold cross-validation.  On a ``-traj`` file without a ``mapping``, ``-cg_method cgae`` learns the
+atom -> bead map on the device first and ``-cg_method newman`` partitions the bond graph there (cgmap.py, datasets.py:190-249,
+277-312, 373-385); ``backbonepartition``, ``seqpartition`` and ``random`` are seeded.  Frames come either from ``--synthetic`` (uniform random
 coordinates of the dataset's shape) or from ``-traj file.npz`` -- a trajectory
 converted offline by ``tools/traj_to_npz.py`` (xyz [T,n,3] in Angstrom, z [n], bonds, optional
 atom -> bead ``mapping``), which goes through the on-device ``build_dataset`` (datasets.py:459-506:
@@ -49,6 +50,10 @@ from . import data as cgdata
 from .train import build_model, optim_dict
 from .trainer import Trainer
 
+# what the JSON summary's "cg_mapping" block shows of a mapping method's info: the learner's six keys, and for the
+# partition methods whichever of theirs the info carries
+CG_MAPPING_KEYS = {"cgae": ("method", "steps", "seconds", "attempts", "loss_recon", "loss_reg")}
+CG_PARTITION_KEYS = ("method", "seconds", "removals", "launches", "form", "mapshuffle", "n_backbone", "seed")
 DATASET_SHAPES = {"dipeptide": 22, "chignolin": 166, "pentapeptide": 94}   # atoms per frame
 
 
@@ -165,9 +170,10 @@ class EarlyStopping:
 def load_trajectory_dataset(params, device):
     """The non-synthetic branch of run_ala.py:124-181 for a file written by tools/traj_to_npz.py: frames (Angstrom),
     atomic numbers and the bond graph come from the file; the atom -> bead map is the file's ``mapping`` or, without
-    one, the map learned from the file's frames for ``-cg_method cgae`` (cgmap.select_mapping; under data parallel every
-    rank learns the same map from the same seed) and contiguous equal blocks of atoms for every other method (the
-    graph-partition mappings -- newman / backbone partition, datasets.py:277-301 -- are out of scope); then
+    one, what ``-cg_method`` says (cgmap.select_mapping): the map learned from the file's frames for ``cgae`` (under data
+    parallel every rank learns the same map from the same seed), the Girvan-Newman partition of the file's bond graph for
+    ``newman`` (with ``-mapshuffle``), the seeded ``backbonepartition`` / ``seqpartition`` / ``random``, and contiguous equal
+    blocks of atoms for every other name (``minimal`` / ``alpha`` need atom names, which the file does not carry); then
     ``build_dataset`` on the device (datasets.py:459-506).  Returns (dataset, mapping, learner's info or None)."""
     with np.load(params["traj"]) as f:
         need = {"xyz", "z", "bonds"}
@@ -176,7 +182,8 @@ def load_trajectory_dataset(params, device):
         xyz, z, bonds = f["xyz"], f["z"], f["bonds"]
         mapping = f["mapping"] if "mapping" in f.files else None
     # the learner sees the whole file (learn_map takes the trajectory, not the -ndata cut: datasets.py:190-197)
-    mapping, map_info = cgmap.select_mapping(params["cg_method"], mapping, xyz, params["n_cgs"], params["cgae_reg_weight"], device)
+    mapping, map_info = cgmap.select_mapping(params["cg_method"], mapping, xyz, params["n_cgs"], params["cgae_reg_weight"], device,
+                                             z=z, bonds=bonds, mapshuffle=params.get("mapshuffle", 0.0), seed=123)
     xyz = xyz[: params["ndata"]]
     n_cgs = int(mapping.max()) + 1
     if params["n_cgs"] and params["n_cgs"] != n_cgs:
@@ -503,8 +510,8 @@ def run(params) -> dict:
     return {**dist, "epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
             "graph_replays": trainer.replays, "test_stats": test_stats,
-            **({"cg_mapping": {k: map_info[k] for k in ("method", "steps", "seconds", "attempts", "loss_recon", "loss_reg")}}
-               if map_info else {})}
+            **({"cg_mapping": {k: map_info[k] for k in CG_MAPPING_KEYS.get(map_info.get("method"), CG_PARTITION_KEYS)
+                               if k in map_info}} if map_info else {})}
 
 
 def main(argv=None):

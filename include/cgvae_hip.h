@@ -1097,6 +1097,52 @@ int cgv_superpose(const float* a, const float* b, const int32_t* sel /*[m]*/, in
                   int off_b, int same, double* row_min, int32_t* row_arg, double* col_min, int32_t* col_arg,
                   double* dense /*[sa,sb] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K18  Girvan-Newman partition of the bond graph (`-cg_method newman`) -- replaces get_partition
+ * (CoarseGrainingVAE/datasets.py:373-385: networkx.community.girvan_newman): remove the live edge of highest betweenness
+ * until the graph has n_cgs connected components.
+ *   rowptr [n+1], col [2m], edge_id [2m] int32   CSR of the undirected graph over atoms: every edge fills one slot of each
+ *                           endpoint's row, edge_id names its undirected edge 0..m-1.  No self loops, no edge twice, col in
+ *                           [0, n), edge_id in [0, m): the CALLER guarantees this (cgmap.bond_csr builds it).
+ *   edges  [m,2] int32      the endpoints of edge e
+ *   alive  [m]   int32      != 0: the edge is still in the graph
+ * cgv_newman_betweenness (no reference line of its own: networkx.edge_betweenness_centrality inside girvan_newman): bet [m]
+ *   fp64 = sum over ALL sources s of Brandes' dependency of s on the edge (every unordered pair counts twice; networkx
+ *   scales the same sums by a constant), over all connected components at once; 0 for an edge that is not alive.
+ *   Launches: a grid of cgv_newman_groups(n, groups) workgroups, each running a contiguous range of ceil(n / groups) sources
+ *   one after the other (groups = 0: the rule, at most 512) and writing one partial row [m]; then one workgroup adds the
+ *   rows in row order.  Path counts and dependencies are fp64, every sum has a fixed order, there is no floating-point
+ *   atomic: the same bits on every run, and in both forms.
+ * cgv_newman_components (datasets.py:363-371, parition2mapping over nx.connected_components): labels [n] int32 = the lowest
+ *   atom index of the atom's component under `alive`; state[0] = number of components, state[1] = 0.  Bead k of the
+ *   reference's numbering is the component with the k-th smallest label.
+ * cgv_newman_partition (datasets.py:373-385): enqueues `removals` rounds of three launches on `stream` --
+ *   betweenness; reduce + choose + remove: among the live edges whose betweenness is within a relative 1e-9 of the maximum
+ *   the one with the lowest (min(u,v), max(u,v)) goes (for edges listed in sorted order: networkx's first maximum whenever
+ *   its values tie exactly), alive[e] = 0, log[state[1]++] = e; components: a BFS from one endpoint of the removed edge,
+ *   and when the other is not reached both sides are relabelled and state[0] goes up.
+ *   Every launch returns at once when state[0] >= n_cgs, so the caller may enqueue a batch and read state[0] (4 bytes)
+ *   once per batch; rounds enqueued after the end change nothing.  Needs labels / state from cgv_newman_components (or
+ *   from earlier rounds) and log [m] int32.  No launch waits for another workgroup.
+ * form: CGV_NEWMAN_RESIDENT -- a workgroup's state (level, sigma, delta per atom, its partial row, the live adjacency) in
+ *   LDS, needs cgv_newman_resident_fits(n, m); CGV_NEWMAN_STREAMED -- the same state in the workspace.
+ * workspace: cgv_newman_workspace_bytes(n, m, form, groups) bytes, 256-byte aligned; the same form and groups in every call
+ *   that shares it; contents need not survive between calls.
+ * Limits: n <= 2^20, m <= 2^22; beyond them the calls fail (CGV_E_BADARG) before any launch. */
+#define CGV_NEWMAN_RESIDENT 1
+#define CGV_NEWMAN_STREAMED 2
+int cgv_newman_resident_fits(int n, int m);
+int cgv_newman_groups(int n, int groups);
+size_t cgv_newman_workspace_bytes(int n, int m, int form, int groups);
+int cgv_newman_betweenness(const int32_t* rowptr, const int32_t* col, const int32_t* edge_id, const int32_t* alive, int n, int m,
+                           int form, int groups, double* bet /*[m]*/, void* workspace, size_t workspace_bytes, void* stream);
+int cgv_newman_components(const int32_t* rowptr, const int32_t* col, const int32_t* edge_id, const int32_t* edges /*[m,2]*/,
+                          const int32_t* alive, int n, int m, int form, int groups, int32_t* labels /*[n]*/,
+                          int32_t* state /*[2]*/, void* workspace, size_t workspace_bytes, void* stream);
+int cgv_newman_partition(const int32_t* rowptr, const int32_t* col, const int32_t* edge_id, const int32_t* edges /*[m,2]*/,
+                         int32_t* alive, int32_t* labels /*[n]*/, int32_t* state /*[2]*/, int32_t* log /*[m]*/, int n, int m,
+                         int n_cgs, int removals, int form, int groups, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,8 @@ Inputs:
     anything mdtraj loads        python tools/traj_to_npz.py traj.xtc out.npz --top protein.pdb     (only if mdtraj is importable)
 Bonds, when not given and not in a topology, are inferred from the first frame: i-j bonded iff d_ij < 1.2 (r_i + r_j)
 (covalent radii).  --stride / --max-frames thin the trajectory.
+--cg_method newman --n_cgs N bakes the Girvan-Newman partition of the bond graph into the file as its ``mapping``
+(cgmap.partition_newman: this one option needs the package and a GPU; --mapping wins over it).
 """
 import argparse
 import sys
@@ -62,6 +64,9 @@ def main(argv=None):
     ap.add_argument("--bonds", help="text file: two atom indices per line")
     ap.add_argument("--mapping", help="text file: one bead index per atom")
     ap.add_argument("--traj-starts", help="text file: the first frame (after --stride / --max-frames) of every independent trajectory")
+    ap.add_argument("--cg_method", choices=["newman"], help="compute the mapping from the bond graph (with --n_cgs)")
+    ap.add_argument("--n_cgs", type=int, help="number of beads of --cg_method")
+    ap.add_argument("--device", default="cuda:0", help="device of --cg_method")
     ap.add_argument("--stride", type=int, default=1)
     ap.add_argument("--max-frames", type=int, default=None)
     a = ap.parse_args(argv)
@@ -98,6 +103,15 @@ def main(argv=None):
         out["mapping"] = np.loadtxt(a.mapping, dtype=np.int64).reshape(-1)
         if out["mapping"].shape[0] != z.shape[0]:
             raise SystemExit("mapping length differs from the number of atoms")
+    elif a.cg_method:
+        if not a.n_cgs:
+            raise SystemExit("--cg_method needs --n_cgs")
+        import os
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from coarsegrainingvae_amd import cgmap
+        mapping, info = cgmap.partition_newman(bonds, z.shape[0], a.n_cgs, device=a.device)
+        out["mapping"] = mapping.numpy().astype(np.int64)
+        print(f"newman mapping: {info['removals']} edges removed in {info['seconds']:.3f} s ({info['form']} form)")
     if a.traj_starts:
         starts = np.loadtxt(a.traj_starts, dtype=np.int64).reshape(-1)
         if starts.shape[0] == 0 or starts[0] != 0 or (np.diff(starts) <= 0).any() or starts[-1] >= xyz.shape[0]:
