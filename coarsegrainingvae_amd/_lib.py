@@ -233,6 +233,12 @@ PROTOTYPES = {
     "cgv_newman_betweenness": (_i, [_p] * 4 + [_i] * 4 + [_p, _p, _sz, _p]),
     "cgv_newman_components": (_i, [_p] * 5 + [_i] * 4 + [_p, _p, _p, _sz, _p]),
     "cgv_newman_partition": (_i, [_p] * 8 + [_i] * 6 + [_p, _sz, _p]),
+    "cgv_baseline_resident_fits": (_i, [_i, _i, _i, _i]),
+    "cgv_baseline_workspace_bytes": (_sz, [_i] * 7),
+    "cgv_baseline_steps": (_i, [_i, _i, _i] + [_p] * 4 + [_i, _p, C.c_int64] + [_i] * 5 + [_p, _p, _p, _i, C.c_int64, _i, _f] +
+                           [C.c_double] * 4 + [_p, _p, _p, _sz, _p]),
+    "cgv_baseline_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_baseline_loss": (_i, [_p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _sz, _p]),
 }
 
 

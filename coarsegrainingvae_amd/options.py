@@ -35,6 +35,7 @@ HOST = {
     "strip_split": 1,       # weight gradients of layers with 32 .. 96 operand rows (bead-level layers of a large bead batch, gathered rows of 4 - 8 ranks): 1 from 64 rows on strips on the bf16 matrix path with split operands (x split once per problem, g once per strip), 0 fp32 MFMA strips, 2 split strips at every row count (tests)
     "cgae_form": 0,         # mapping learner (cgmap.py): 0 rule of cgv_cgae_resident_fits (state in one workgroup's LDS when n_atoms x n_cgs fits), 1 resident, 2 streamed (tests force either at a small size)
     "newman_form": 0,       # Girvan-Newman partition (cgmap.partition_newman): 0 rule of cgv_newman_resident_fits (a workgroup's per-source state in LDS when n_atoms / n_edges fit), 1 resident, 2 streamed (tests force either at a small size)
+    "baseline_form": 0,     # linear baselines (baseline.py): 0 rule of cgv_baseline_resident_fits (matrix and Adam moments in one workgroup's LDS when they fit), 1 resident, 2 global (tests force either at a small size)
     "decoder_dense": 0,     # full-width products of the fused decoder loop: 0 four-column blocks (cgv_decoder_dense_fwd), 1 skinny_fwd_k
 }
 _DEFAULTS = dict(HOST)

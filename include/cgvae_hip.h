@@ -1143,6 +1143,63 @@ int cgv_newman_partition(const int32_t* rowptr, const int32_t* col, const int32_
                          int32_t* alive, int32_t* labels /*[n]*/, int32_t* state /*[2]*/, int32_t* log /*[m]*/, int n, int m,
                          int n_cgs, int removals, int form, int groups, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K19  baseline models (`run_baseline -model linear | equilinear | mlp`) -- replaces the optimiser loop of
+ * scripts/run_baseline.py:121-176 (losses 86-92, 147-149; torch.optim.Adam 304) on Baseline (CoarseGrainingVAE/baseline.py:
+ * 8-36) and EquiLinear (baseline.py:387-443) under the fixed pooler CGpool (diffpoolvae.py:105-195: cg = bead means), and
+ * the loss of the MLP (baseline.py:109-147).  Both linear models are one matrix over feature vectors of the bead means:
+ *   dx[b,a,:] = sum_c P(a,c) U[b,c,:]
+ *   CGV_BASELINE_LINEAR      B [K,n], P(a,c) = B[c,a], C = K; U[b,c] = cg[b,c] - mean_atoms(xyz[b]);
+ *                            recon = dx against xyz - mean_atoms(xyz)
+ *   CGV_BASELINE_EQUILINEAR  B [n, K knn], P(a,c) = B[a,c], C = K knn; U[b, i knn + (c-1)] = cg[b,c] - cg[b,i], c = 1..knn
+ *                            (c is a bead index, as in the reference: it takes nonzero() of the SORTED distances, so the
+ *                            pair's second index is the rank position used as a bead id); recon[b,a] = cg[b,m(a)] -
+ *                            mean_{a' in bead m(a)} dx[b,a'] + dx[b,a] against xyz.  1 <= knn <= K - 1.
+ *   loss_recon = mean over b n 3 of (recon - target)^2; loss_dist = mean over (b, e) of (|recon_i - recon_j| - |x_i - x_j|)^2
+ *   over the hyperedges e = (i, j); loss = loss_recon + gamma loss_dist; Adam (bias correction, no weight decay) on B.
+ * Two deliberate deviations from the reference, in cgv_baseline_steps and cgv_baseline_loss alike: a hyperedge whose
+ * RECONSTRUCTED length is exactly 0 contributes 0 to the gradient (reference: NaN), and an empty hyperedge list gives
+ * loss_dist = 0 (reference: NaN).
+ *   B, mB, vB               the parameter and its Adam moments in the reference's layout, updated in place (mB, vB may be
+ *                           NULL in forward mode)
+ *   frames [n_frames,n,3]   as they are (not centred)
+ *   order, order_len, n_train, batch, step0, steps      the schedule, exactly as in cgv_cgae_steps: the last, partial batch
+ *                           of an epoch is kept and its means divide by its own counts; Adam's step count is step + 1
+ *   mapping [n] int32 in [0,K), bead_sizes [K] int32 (> 0: the CALLER guarantees it), edges [E,2] int32 hyperedges of the
+ *   molecule shared by all frames (indices outside [0,n) are clamped; E may be 0)
+ *   loss_log [steps,2]      (loss_recon, loss_dist) of every step of this call
+ *   probe  optional         of the call's LAST step: xyz_recon [batch,n,3], then (train mode) the gradient in B's layout
+ *   mode   CGV_BASELINE_TRAIN, or CGV_BASELINE_FORWARD: forward and losses only, B and the moments untouched
+ * form: CGV_BASELINE_RESIDENT -- B, both moments, the bead means and U in the LDS of the one workgroup that runs the call,
+ *   needs cgv_baseline_resident_fits(kind, n, C, batch) (3 n C + 6 batch (3 C + 1) + 32 floats within 160 KB: the small per-batch arrays are doubles);
+ *   CGV_BASELINE_GLOBAL -- the same single-workgroup loop on the caller's arrays in place, small arrays in the workspace.
+ *   Every sum has a fixed order and there is no floating-point atomic: a call of `steps` steps equals `steps` calls of one,
+ *   a repeated call gives the same bits, and the two forms give the same bits.
+ * Cap: n C, batch n, batch C, batch E and 2 E below 2^24 and K <= n; beyond it the calls fail (CGV_E_BADARG) before any
+ *   launch.  The global form is correct at every size below the cap.
+ * workspace: cgv_baseline_workspace_bytes(...), 256-byte aligned, contents need not survive between calls.
+ * cgv_baseline_loss: for xyz_recon, xyz [b,n,3] (the MLP's output and its target) losses[0] = loss_recon, losses[1] =
+ *   loss_dist and grad [b,n,3] = d(loss_recon + gamma loss_dist) / d xyz_recon, one launch of b blocks; the blocks' loss
+ *   partials are added in frame order by the last block to arrive (no floating-point atomic: the same bits on every run).
+ *   workspace: cgv_baseline_loss_workspace_bytes(b, n, E) bytes whose first 256 are ZERO before the first call (every call
+ *   leaves them zero); one call at a time per workspace.  Cap: b <= 65535, b n and b E below 2^24, n E below 2^28. */
+#define CGV_BASELINE_LINEAR 1
+#define CGV_BASELINE_EQUILINEAR 2
+#define CGV_BASELINE_RESIDENT 1
+#define CGV_BASELINE_GLOBAL 2
+#define CGV_BASELINE_TRAIN 0
+#define CGV_BASELINE_FORWARD 1
+int cgv_baseline_resident_fits(int kind, int n_atoms, int C, int batch);
+size_t cgv_baseline_workspace_bytes(int kind, int n, int K, int knn, int batch, int E, int form);
+int cgv_baseline_steps(int kind, int form, int mode, float* B, float* mB, float* vB, const float* frames, int n_frames,
+                       const int32_t* order, int64_t order_len, int n_train, int batch, int n, int K, int knn,
+                       const int32_t* mapping, const int32_t* bead_sizes, const int32_t* edges /*[E,2]*/, int E, int64_t step0,
+                       int steps, float gamma, double lr, double beta1, double beta2, double eps, float* loss_log /*[steps,2]*/,
+                       float* probe, void* workspace, size_t workspace_bytes, void* stream);
+size_t cgv_baseline_loss_workspace_bytes(int b, int n, int E);
+int cgv_baseline_loss(const float* xyz_recon, const float* xyz, const int32_t* edges /*[E,2]*/, int b, int n, int E, float gamma,
+                      float* losses /*[2]*/, float* grad /*[b,n,3]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
