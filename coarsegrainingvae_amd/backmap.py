@@ -17,6 +17,8 @@ launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No a
         -out out.npz [-frames_per_launch M] [-seed S] [--pair_rmsd] [--require_valid all|heavy -max_rounds R]
         [--dist_stats [-ref atoms.npz]] [--tica_stats [-tica_lag 100] [-tica_bins 50]]
         [--cov_stats [-cov_thresholds 0.5 1.0 2.0] [-cov_atoms heavy]]
+        [--contact_stats [-contact_cutoff 4.5] [-contact_atoms heavy|all] [-contact_exclude 3]
+         [-contact_groups none|bead|residue]]
 
 ``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
 the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
@@ -43,6 +45,14 @@ some reference frame?  ``coverage.compare``: superposed RMSD (K17) between all `
 ``-ref`` (default: those of ``-traj``) over the ``-cov_atoms`` (``heavy`` or ``all``): COV-R / MAT-R, COV-P / MAT-P at the
 ``-cov_thresholds`` (Angstrom), with the even / odd floor of the reference, go to ``cov_stats.json`` next to ``-out``, the
 short form into the summary line under ``"cov_stats"``.  Needs a topology (for the elements).
+
+``--contact_stats``: do the backmapped structures pack as the reference does?  ``contacts.compare``: the contact
+probability of every pair of ``-contact_atoms`` (``heavy`` or ``all``) closer than ``-contact_cutoff`` Angstrom and more
+than ``-contact_exclude`` bonds apart (K20) -- or, with ``-contact_groups bead | residue``, of every pair of beads of the
+run's mapping or of residues of a peptide -- over all ``T * K`` structures against the frames of ``-ref`` (default: those
+of ``-traj``), the fraction of native contacts and the radius of gyration of every structure, with the even / odd floor of
+the reference, go to ``contact_stats.json`` next to ``-out``, the short form into the summary line under
+``"contact_stats"``.  Needs a topology.  These switches are absent from the parsed arguments unless given.
 """
 from __future__ import annotations
 
@@ -297,7 +307,26 @@ def build_parser() -> argparse.ArgumentParser:
                    help="coverage and precision of the output against -ref by superposed RMSD; writes cov_stats.json next to -out")
     p.add_argument("-cov_thresholds", type=float, nargs="+", default=[0.5, 1.0, 2.0], help="RMSD thresholds of --cov_stats in Angstrom")
     p.add_argument("-cov_atoms", choices=("heavy", "all"), default="heavy", help="atoms that --cov_stats superposes")
+    # absent from the namespace unless given (CONTACT_DEFAULTS holds what they default to): a command line without them
+    # parses to what it parsed to before they existed
+    p.add_argument("--contact_stats", action="store_true", default=argparse.SUPPRESS,
+                   help="contact probability maps, native contacts and Rg of the output against -ref; writes contact_stats.json next to -out")
+    p.add_argument("-contact_cutoff", type=float, default=argparse.SUPPRESS, help="contact distance of --contact_stats in Angstrom (4.5)")
+    p.add_argument("-contact_atoms", choices=("heavy", "all"), default=argparse.SUPPRESS, help="atoms that --contact_stats looks at (heavy)")
+    p.add_argument("-contact_exclude", type=int, default=argparse.SUPPRESS,
+                   help="pairs at most this many bonds apart are no contacts (3)")
+    p.add_argument("-contact_groups", choices=("none", "bead", "residue"), default=argparse.SUPPRESS,
+                   help="contacts between atoms (none), beads of the run's mapping, or residues of a peptide (none)")
     return p
+
+
+CONTACT_DEFAULTS = {"contact_stats": False, "contact_cutoff": 4.5, "contact_atoms": "heavy", "contact_exclude": 3,
+                    "contact_groups": "none"}
+
+
+def contact_args(args) -> dict:
+    """The ``--contact_stats`` switches of parsed arguments, with their defaults where they were not given."""
+    return {k: getattr(args, k, v) for k, v in CONTACT_DEFAULTS.items()}
 
 
 def _npz(path: str, need) -> dict:
@@ -318,9 +347,10 @@ def read_inputs(args, params, device=None) -> dict:
     z = bonds = ref_xyz = None
     dist_stats, tica_stats = getattr(args, "dist_stats", False), getattr(args, "tica_stats", False)
     cov_stats = getattr(args, "cov_stats", False)
-    need_ref, starts = dist_stats or tica_stats or cov_stats, None
+    contact = contact_args(args)
+    need_ref, starts = dist_stats or tica_stats or cov_stats or contact["contact_stats"], None
     if getattr(args, "ref", None) and not need_ref:
-        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats")
+        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats / --contact_stats")
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
@@ -348,7 +378,7 @@ def read_inputs(args, params, device=None) -> dict:
     if args.require_valid and bonds is None:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
     if need_ref:
-        switch = "--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats"
+        switch = "--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats" if cov_stats else "--contact_stats"
         if bonds is None:
             raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
@@ -377,6 +407,17 @@ def read_inputs(args, params, device=None) -> dict:
                 raise SystemExit("--cov_stats: -cov_thresholds must be positive RMSDs in Angstrom")
             if coverage.select_atoms(z, args.cov_atoms).shape[0] == 0:
                 raise SystemExit(f"--cov_stats: the topology has no {args.cov_atoms} atoms to superpose")
+        if contact["contact_stats"]:
+            from . import contacts, coverage
+            if not contact["contact_cutoff"] > 0 or contact["contact_exclude"] < 0:
+                raise SystemExit("--contact_stats: -contact_cutoff must be a positive distance in Angstrom, -contact_exclude >= 0")
+            if coverage.select_atoms(z, contact["contact_atoms"]).shape[0] < 2:
+                raise SystemExit(f"--contact_stats: the topology has fewer than two {contact['contact_atoms']} atoms")
+            if contact["contact_groups"] == "residue":
+                try:
+                    contacts.groups_of(z, bonds, None, "residue")
+                except ValueError as err:
+                    raise SystemExit(f"--contact_stats: {err}")
     if params.get("cg_radius_graph") and bonds is None:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
     return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if need_ref else {}),
@@ -444,6 +485,16 @@ def run(args) -> dict:
         with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "cov_stats.json"), "w") as f:
             json.dump(stats, f)
         dist["cov_stats"] = coverage.summary_of(stats)
+    contact = contact_args(args)
+    if contact["contact_stats"]:
+        from . import contacts
+        stats = contacts.compare(inp["ref_xyz"], res["xyz"].reshape(T * K, -1, 3), z, bonds, atoms=contact["contact_atoms"],
+                                 cutoff=contact["contact_cutoff"], exclude=contact["contact_exclude"],
+                                 groups=None if contact["contact_groups"] == "none" else contact["contact_groups"],
+                                 mapping=mapping, device=device)
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "contact_stats.json"), "w") as f:
+            json.dump(stats, f)
+        dist["contact_stats"] = contacts.summary_of(stats)
 
     def mean(key):
         if key not in res:

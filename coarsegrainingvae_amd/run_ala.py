@@ -120,6 +120,10 @@ def build_extras_parser() -> argparse.ArgumentParser:
     p.add_argument("--cov_eval", action="store_true", default=False,
                    help="after the evaluation, coverage and precision of the hold-out frames' prior samples against those "
                         "frames by superposed heavy-atom RMSD (coverage.compare): cov_stats.json in the log directory")
+    # absent from the parsed arguments unless given: without it they are what they were before the switch existed
+    p.add_argument("--contact_eval", action="store_true", default=argparse.SUPPRESS,
+                   help="after the evaluation, heavy-atom contact maps, native contacts and Rg of the hold-out frames' prior "
+                        "samples against those frames (contacts.compare): contact_stats.json in the log directory")
     return p
 
 
@@ -127,7 +131,7 @@ def stored_params(params: dict) -> dict:
     """What ``modelparams.json`` records of the parameters: a switch of ``build_extras_parser`` that is off leaves the
     file as it was before the switch existed (its key, and the keys of its options, are left out)."""
     off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"),
-                               ("cov_eval", "cov_eval"))
+                               ("cov_eval", "cov_eval"), ("contact_eval", "contact_eval"))
            if not params.get(switch)]
     return {k: v for k, v in params.items() if k not in off}
 
@@ -300,6 +304,8 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
         stats["tica_stats"] = tica_eval(params, dataset, val_idx, samples, device, logdir)
     if params.get("cov_eval"):
         stats["cov_stats"] = cov_eval(dataset, val_idx, samples, device, logdir)
+    if params.get("contact_eval"):
+        stats["contact_stats"] = contact_eval(dataset, val_idx, samples, device, logdir)
     return stats
 
 
@@ -338,6 +344,25 @@ def cov_eval(dataset, val_idx, samples, device, logdir):
         with open(os.path.join(logdir, "cov_stats.json"), "w") as f:
             json.dump(full, f)
     return coverage.summary_of(full)
+
+
+def contact_eval(dataset, val_idx, samples, device, logdir):
+    """``--contact_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
+    tuple) by the contacts of their heavy atoms: contact probability maps, native contacts, Rg.  Writes
+    ``contact_stats.json``; returns ``contacts.summary_of``, which stays in the summary's ``"test_stats"``, or ``None``
+    when there is nothing to compare (fewer than two hold-out frames, or frames of different molecules)."""
+    from . import contacts
+    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
+        print("--contact_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
+        return None
+    frame = dataset[val_idx[0]]
+    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
+    atoms = "heavy" if (z != 1).sum() >= 2 else "all"
+    full = contacts.compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy(), atoms=atoms, device=device)
+    if logdir:
+        with open(os.path.join(logdir, "contact_stats.json"), "w") as f:
+            json.dump(full, f)
+    return contacts.summary_of(full)
 
 
 def tica_eval(params, dataset, val_idx, samples, device, logdir):

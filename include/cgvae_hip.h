@@ -1200,6 +1200,57 @@ size_t cgv_baseline_loss_workspace_bytes(int b, int n, int E);
 int cgv_baseline_loss(const float* xyz_recon, const float* xyz, const int32_t* edges /*[E,2]*/, int b, int n, int E, float gamma,
                       float* losses /*[2]*/, float* grad /*[b,n,3]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K20  contact maps of an ensemble -- which atoms (or groups of atoms: beads, residues) touch, how compact a structure is,
+ * and whether it has the contacts the data has: contact probability maps, the fraction of native contacts Q and the
+ * radius of gyration.  Nothing in the reference computes them.
+ *   xyz [n_structures,n_atoms,3] fp32
+ *   sel [m] int32, 1 <= m <= n_atoms          the atoms that count, in any order; all indices below are positions in sel.
+ *                                             An index outside [0, n_atoms) reads atom 0 (the host wrapper refuses such a
+ *                                             selection); nothing is read out of bounds.
+ *   excluded [m, ceil(m/32)] uint32           bit (j & 31) of word [i][j >> 5]: the pair (i, j) never counts (bonded
+ *                                             neighbours).  The CALLER keeps it symmetric; the diagonal never counts.
+ *   native (may be NULL)                      the same layout (cgv_contact_group_counts: [n_groups, ceil(n_groups/32)] over
+ *                                             groups): the pairs whose contacts n_native counts
+ *   cutoff2 fp32 >= 0                         the squared cutoff
+ * A pair (i, j), i != j, not excluded, is in contact in structure s iff (dx*dx + dy*dy) + dz*dz < cutoff2, fp32 with
+ * every operation individually rounded (csrc/sq_dist.h: sq_dist2) and strict <: a host that restates the sum gets every
+ * integer below exactly.
+ *   counts [m,m] int32                        the structures in which (i, j) is in contact are ADDED to both [i][j] and
+ *                                             [j][i] (the diagonal is not touched): a caller cuts a long ensemble into
+ *                                             launches and zeroes the table once.  Total structures < 2^31: the CALLER's.
+ *   n_contacts [n_structures] int32           overwritten: unordered pairs in contact in structure s
+ *   n_native   [n_structures] int32           overwritten: those of them that are in `native` (0 without one)
+ *   rg2 [n_structures] fp64                   overwritten: mean over sel of |x - centroid|^2, fp64 from widened
+ *                                             coordinates, two passes, fixed summation tree (may be NULL in the group call)
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate inside sel.  It
+ *                                             adds nothing to counts, has n_contacts = n_native = -1 and rg2 = NaN.
+ * cgv_contact_group_counts: sel is sorted so that the atoms of group g are the positions group_start[g] ..
+ *   group_start[g + 1] - 1 (group_start [n_groups + 1] int32, ascending from 0 to m).  Groups A != B are in contact in
+ *   structure s iff ANY non-excluded pair (a in A, b in B) is; group_counts [n_groups,n_groups] int32 is added to like
+ *   counts, n_contacts / n_native count pairs of groups.  (Not derivable from counts: the "any" is per structure.)
+ * Launches: one wave per structure gathers sel into a packed copy [n_structures, m] float4 in the workspace and computes
+ *   rg2 and bad (a bad structure's copy is NaN: in contact with nothing).  cgv_contact_counts: grid (tiles of 128 columns,
+ *   tiles of 64 rows, slices of the structure axis) x 256 threads over the tiles that hold a pair i < j; a thread keeps the
+ *   32 counters of its row and its wave's 32 columns in registers, 8 structures at a time pass through 24 KB of LDS; the
+ *   slices -- as many as bring the grid to 1024 blocks, of at least 64 structures -- meet in integer atomicAdd.
+ *   cgv_contact_group_counts: grid (n_groups, n_groups, slices) x one wave, 64 structures per pass.
+ *   Integer sums do not depend on their order and rg2 uses no atomic: the same bits on every run.
+ * workspace: cgv_contact_workspace_bytes(n_structures, m) bytes, 16-byte aligned, contents need not survive.
+ * Limits: m <= cgv_contact_max_atoms(), n_structures <= cgv_contact_max_structures() per launch, n_groups <= min(m, 4096);
+ * beyond a limit the call fails (CGV_E_BADARG) before any launch.  Bound: see DESIGN.md (K20 row). */
+int cgv_contact_max_atoms(void);
+int cgv_contact_max_structures(void);
+size_t cgv_contact_workspace_bytes(int n_structures, int m);
+int cgv_contact_counts(const float* xyz, const int32_t* sel /*[m]*/, const uint32_t* excluded, const uint32_t* native /*or NULL*/,
+                       int n_structures, int n_atoms, int m, float cutoff2, int32_t* counts /*[m,m]*/, int32_t* n_contacts,
+                       int32_t* n_native, double* rg2, int32_t* bad, void* workspace, size_t workspace_bytes, void* stream);
+int cgv_contact_group_counts(const float* xyz, const int32_t* sel /*[m]*/, const int32_t* group_start /*[n_groups+1]*/,
+                             const uint32_t* excluded, const uint32_t* native /*or NULL*/, int n_structures, int n_atoms, int m,
+                             int n_groups, float cutoff2, int32_t* group_counts /*[n_groups,n_groups]*/, int32_t* n_contacts,
+                             int32_t* n_native, double* rg2 /*or NULL*/, int32_t* bad, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
