@@ -109,9 +109,9 @@ __device__ __forceinline__ float act_bwd(float z, int act) {
 
 // ------------------------------------------------------------------ slice sums
 // A gradient operand handed over as "base + row-slice partial sums": value(i) = base[i] + sum_s slices[s * stride + i],
-// s ascending (deterministic).  This is how the split backward-input products (skinny_gemm.hip: the row slices of one
-// product each leave a partial [M, K] matrix) reach their consumers without a reduction launch in between: the consumer
-// adds the slices while it loads its operand.  base or slices may be NULL (n = 0 when slices is NULL).
+// s ascending (deterministic): the consumer adds the slices while it loads its operand.  The operand type of the
+// update.hip backward kernels, whose entry points hand over a plain matrix (base alone, n = 0).  base or slices may be
+// NULL (n = 0 when slices is NULL).
 struct SliceSum {
   const float* base;
   const float* slices;
@@ -131,7 +131,7 @@ __device__ __forceinline__ float slice_sum_at(const SliceSum& ss, size_t i) {
   return acc;
 }
 
-// ------------------------------------------------------------------ fused optimiser (optim.hip, skinny_gemm.hip)
+// ------------------------------------------------------------------ fused optimiser (optim.hip, wgrad_grouped.hip, wgrad_gathered.hip)
 // state[] layout (device floats) written by optim_finalize, read by every parameter pass
 enum { ST_STEP = 0, ST_NORM = 1, ST_CLIP = 2, ST_BC1 = 3, ST_BC2SQRT = 4, ST_SKIP = 5, ST_NSKIPPED = 6 };
 

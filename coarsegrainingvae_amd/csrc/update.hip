@@ -141,12 +141,6 @@ int cgv_update_vec_from_rows(const float* rows, const float* res, float* vec, in
   CGV_EW_LAUNCH(cgv::update_vec_from_rows, (cgv::SliceSum{rows, nullptr, 0, 0}), res, vec, n_nodes, n_feat);
 }
 
-int cgv_update_vec_from_rows_slices(const float* rows_slices, int n_slices, int64_t slice_stride, const float* res, float* vec,
-                                    int n_nodes, int n_feat, void* stream) {
-  CGV_REQUIRE(rows_slices && vec && n_slices >= 1 && slice_stride >= (int64_t)3 * n_nodes * n_feat, "bad argument");
-  CGV_EW_LAUNCH(cgv::update_vec_from_rows, (cgv::SliceSum{nullptr, rows_slices, n_slices, slice_stride}), res, vec, n_nodes, n_feat);
-}
-
 int cgv_update_norm_stack_fwd(const float* s, const float* Vv, float* stack, int n_nodes, int n_feat, int ld, void* stream) {
   CGV_REQUIRE(s && Vv && stack && ld >= n_feat, "bad argument");
   CGV_EW_LAUNCH(cgv::update_norm_stack_fwd, s, Vv, stack, n_nodes, n_feat, ld);
@@ -157,19 +151,6 @@ int cgv_update_norm_stack_bwd(const float* gstack, const float* Vv, const float*
   CGV_REQUIRE(gstack && Vv && stack && g_s && gVv && ld >= n_feat, "bad argument");
   CGV_EW_LAUNCH(cgv::update_norm_stack_bwd, (cgv::SliceSum{gstack, nullptr, 0, 0}), Vv, stack, (cgv::SliceSum{g_res, nullptr, 0, 0}),
                 g_s, gVv, n_nodes, n_feat, ld, accumulate);
-}
-
-int cgv_update_norm_stack_bwd_slices(const float* gstack_slices, int n_slices, int64_t slice_stride, const float* Vv,
-                                     const float* stack, const float* g_res_base, const float* g_res_slices, int n_res_slices,
-                                     int64_t res_slice_stride, float* g_s, float* gVv, int n_nodes, int n_feat, int ld,
-                                     int accumulate, void* stream) {
-  CGV_REQUIRE(gstack_slices && Vv && stack && g_s && gVv && ld >= n_feat, "bad argument");
-  CGV_REQUIRE(n_slices >= 1 && slice_stride >= (int64_t)2 * n_nodes * n_feat, "bad slices");
-  CGV_REQUIRE(n_res_slices >= 0 && (n_res_slices == 0 || (g_res_slices && res_slice_stride >= (int64_t)n_nodes * n_feat)),
-              "bad residual slices");
-  CGV_EW_LAUNCH(cgv::update_norm_stack_bwd, (cgv::SliceSum{nullptr, gstack_slices, n_slices, slice_stride}), Vv, stack,
-                (cgv::SliceSum{g_res_base, g_res_slices, g_res_slices ? n_res_slices : 0, res_slice_stride}), g_s, gVv, n_nodes,
-                n_feat, ld, accumulate);
 }
 
 int cgv_update_gate_fwd(const float* U, const float* Vv, const float* a, const float* s_res, const float* v_res, float* ds,
@@ -183,15 +164,6 @@ int cgv_update_gate_bwd(const float* U, const float* Vv, const float* a, const f
                         float* gU, float* gVv, float* ga, int n_nodes, int n_feat, int ld, void* stream) {
   CGV_REQUIRE(U && Vv && a && gU && gVv && ga && ld >= n_feat, "bad argument");
   CGV_EW_LAUNCH(cgv::update_gate_bwd, U, Vv, a, (cgv::SliceSum{g_ds, nullptr, 0, 0}), g_dv, gU, gVv, ga, n_nodes, n_feat, ld);
-}
-
-int cgv_update_gate_bwd_slices(const float* U, const float* Vv, const float* a, const float* g_ds_base,
-                               const float* g_ds_slices, int n_slices, int64_t slice_stride, const float* g_dv, float* gU,
-                               float* gVv, float* ga, int n_nodes, int n_feat, int ld, void* stream) {
-  CGV_REQUIRE(U && Vv && a && gU && gVv && ga && ld >= n_feat, "bad argument");
-  CGV_REQUIRE(n_slices >= 0 && (n_slices == 0 || (g_ds_slices && slice_stride >= (int64_t)n_nodes * n_feat)), "bad slices");
-  CGV_EW_LAUNCH(cgv::update_gate_bwd, U, Vv, a, (cgv::SliceSum{g_ds_base, g_ds_slices, n_slices, slice_stride}), g_dv, gU, gVv, ga,
-                n_nodes, n_feat, ld);
 }
 
 }  // extern "C"

@@ -433,7 +433,7 @@ def scatter_mean(src: torch.Tensor, index: torch.Tensor, dim: int = 0, dim_size:
 
 # ----------------------------------------------------------------------------- decoder tail
 class _TailSlot:
-    """Hand-over between a LAZY ``reconstruct`` (no launch: the coordinates are produced by the loss launch) and the fused
+    """Hand-over between a lazy ``reconstruct`` (no launch: the coordinates are produced by the loss launch) and the fused
     decoder-tail + ELBO launch (``_Elbo`` with ``tail``): the tail's inputs one way, d loss / d V the other way."""
     __slots__ = ("v", "cg_xyz", "chan", "plan", "offset", "out", "g_V", "g_xr", "filled")
 

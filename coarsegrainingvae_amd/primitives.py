@@ -85,7 +85,7 @@ class WeightGradQueue:
     """Deferred, grouped weight gradients.  While ``collect()`` is active (the trainer wraps
     ``loss.backward()`` in it), every skinny linear layer only *registers* its weight-gradient
     problem  gW (+)= (gy * act'(z))^T x ; ``flush()`` then runs ALL of them in one grouped HIP launch
-    (csrc/skinny_gemm.hip: grouped_wgrad_k) writing straight into the gradient arena.  ~66 launches
+    (csrc/wgrad_grouped.hip: grouped_wgrad_t) writing straight into the gradient arena.  ~66 launches
     per step become one, and the weight-gradient writes (the largest traffic of the backward pass)
     stream at HBM speed instead of paying a few microseconds of launch latency each."""
 
@@ -300,7 +300,7 @@ class WeightGradQueue:
 
     def strip_launch(self, table, n_problems, blocks, rows, tag):
         """The strip-layout store launch for the table ``strip_table`` has just built: on the bf16 matrix path with split
-        operands (x split once per problem, g once per strip: csrc/skinny_gemm.hip strip_split_k) for up to 96 operand rows,
+        operands (x split once per problem, g once per strip: csrc/wgrad_gathered.hip strip_split_k) for up to 96 operand rows,
         else on the fp32 MFMA strips."""
         from .options import HOST
         plane_bytes, max_k = self._strip_plan
@@ -366,7 +366,7 @@ class WeightGradQueue:
                 block_begin += nb.value
             table = self.upload(bytes(buf), dev)
             if split:
-                # bf16 matrix path with split operands (fp32-class accuracy, csrc/skinny_gemm.hip wgrad_split128_k)
+                # bf16 matrix path with split operands (fp32-class accuracy, csrc/wgrad_gathered.hip wgrad_split128_k)
                 _lib.call("cgv_grouped_wgrad_split", _lib.ptr(table), len(large), block_begin, _lib.stream_ptr(),
                           tag="grouped_wgrad_tiles")
             else:

@@ -248,7 +248,7 @@ class OperandExchange:
     bead-level weights are 0.36 - 3.2 M elements each (220 MB together): all-reducing them moves ~270 MB per step and
     rank over xGMI rings that are per-link bound.  Here the ranks all-gather the operand rows instead
     (``g = gy * act'(z)`` and ``x``: (N + K) * rows floats per layer, ~7 MB per rank and step) and every rank forms the
-    gradient of the CONCATENATED batch itself with one grouped MFMA launch (csrc/skinny_gemm.hip:
+    gradient of the CONCATENATED batch itself with one grouped MFMA launch (csrc/wgrad_gathered.hip:
     gathered_wgrad_k) -- the sum a single process would compute (scripts/utils.py:110-157 on the whole batch),
     bit-identical on every rank, no reduction tree.  The redundant flops (world x the local product) are noise
     next to the bytes saved.  Layers whose rows are not cheaper than their weights (atom-level layers, big bead

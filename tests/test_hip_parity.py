@@ -2735,7 +2735,7 @@ def test_bead_mean_inside_the_contractive_block_equals_separate_launches(workloa
 @pytest.mark.parametrize("M,N,K,act", [(332, 600, 600, 1), (704, 1800, 600, 1), (129, 132, 260, 0), (2000, 64, 600, 1), (161, 600, 36, 0)])
 def test_split_bf16_weight_gradients_have_fp32_accuracy(M, N, K, act, options):
     """Weight gradients of layers with more than 128 operand rows (autograd of nn.Linear / Dense, modules.py; conv.py:505-563)
-    on the bf16 matrix path with SPLIT operands (csrc/skinny_gemm.hip wgrad_split128_k: three bf16 terms per fp32 value,
+    on the bf16 matrix path with SPLIT operands (csrc/wgrad_gathered.hip wgrad_split128_k: three bf16 terms per fp32 value,
     six products, fp32 accumulation) against fp64 -- and against the fp32 MFMA tiles: the error has to be of the same class
     (north_star's tolerance is 1e-4; fp32 kernels sit at 1e-7).  Operands span 12 orders of magnitude (gradients are tiny,
     activations are not): bf16 keeps the fp32 exponent range, nothing is scaled.  Write and accumulate."""
@@ -3061,7 +3061,7 @@ def test_stream_k_default_dispatch_takes_the_many_row_long_reduction_products(op
 def test_strip_layout_with_split_operands_has_fp32_accuracy(M, N, K, act, options):
     """Weight gradients of layers with 33 .. 96 operand rows (the bead-level Dense layers of a large bead batch: 96 beads of the
     dipeptide batch, 64 of the 2000-atom graph; autograd of modules.py:103-114) on the bf16 matrix path with split operands in
-    the STRIP layout (csrc/skinny_gemm.hip strip_xplanes_k + strip_split_k: x split once per problem, g once per strip)
+    the STRIP layout (csrc/wgrad_gathered.hip strip_xplanes_k + strip_split_k: x split once per problem, g once per strip)
     against fp64 and against the fp32 MFMA strips: same error class.  Operands span 12 orders of magnitude; ragged row /
     column counts; write and accumulate; several problems of different shapes in one table."""
     from coarsegrainingvae_amd.primitives import WeightGradQueue

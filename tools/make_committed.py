@@ -14,7 +14,7 @@ SOURCES = {
     "equi_msg_fwd": ["equi_msg_grp.hip", "equi_msg.hip", "equi_msg_dev.h"],
     "segment_reduce": ["scatter.hip"],
     "optimizer": ["optim.hip"],
-    "rank_update": ["skinny_gemm.hip"],
+    "rank_update": ["wgrad_grouped.hip", "wgrad_gram.hip", "wgrad_record.h", "gemm_dev.h"],
 }
 
 
