@@ -221,6 +221,11 @@ PROTOTYPES = {
     "cgv_contact_workspace_bytes": (_sz, [_i, _i]),
     "cgv_contact_counts": (_i, [_p] * 4 + [_i, _i, _i, _f] + [_p] * 5 + [_p, _sz, _p]),
     "cgv_contact_group_counts": (_i, [_p] * 5 + [_i, _i, _i, _i, _f] + [_p] * 5 + [_p, _sz, _p]),
+    "cgv_align_max_atoms": (_i, []),
+    "cgv_align_max_structures": (_i, []),
+    "cgv_align_wave_fits": (_i, [_i]),
+    "cgv_align_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_align_accumulate": (_i, [_p] * 3 + [_i] * 4 + [_p] * 6 + [_p, _sz, _p]),
     "cgv_cgae_resident_fits": (_i, [_i, _i, _i]),
     "cgv_cgae_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cgv_cgae_steps": (_i, [_i] + [_p] * 7 + [_i, _p, C.c_int64, _i, _i, _i, _i, C.c_int64, _i, _f] + [C.c_double] * 4 +

@@ -19,6 +19,7 @@ launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No a
         [--cov_stats [-cov_thresholds 0.5 1.0 2.0] [-cov_atoms heavy]]
         [--contact_stats [-contact_cutoff 4.5] [-contact_atoms heavy|all] [-contact_exclude 3]
          [-contact_groups none|bead|residue]]
+        [--flex_stats [-flex_atoms heavy|all] [-flex_groups none|bead|residue] [-flex_aligned aligned.npz]]
 
 ``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
 the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
@@ -53,6 +54,15 @@ run's mapping or of residues of a peptide -- over all ``T * K`` structures again
 of ``-traj``), the fraction of native contacts and the radius of gyration of every structure, with the even / odd floor of
 the reference, go to ``contact_stats.json`` next to ``-out``, the short form into the summary line under
 ``"contact_stats"``.  Needs a topology.  These switches are absent from the parsed arguments unless given.
+
+``--flex_stats``: do the backmapped structures move as much as the reference does?  ``flexibility.compare``: all ``T * K``
+structures and the frames of ``-ref`` (default: those of ``-traj``) are each superposed about their own mean structure
+over the ``-flex_atoms`` (``heavy`` or ``all``; K21) and the per-atom fluctuations (RMSF) -- or, with ``-flex_groups bead |
+residue``, those of the beads of the run's mapping or of the residues of a peptide -- are compared, with the even / odd
+floor of the reference: ``flex_stats.json`` next to ``-out``, the short form into the summary line under
+``"flex_stats"``.  ``-flex_aligned file.npz`` also writes the backmapped structures in their mean's frame (``xyz``
+[T*K,n,3]), the mean (``mean``), ``rmsf`` and the selection (``atoms``).  Needs a topology.  These switches, too, are
+absent from the parsed arguments unless given.
 """
 from __future__ import annotations
 
@@ -317,6 +327,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="pairs at most this many bonds apart are no contacts (3)")
     p.add_argument("-contact_groups", choices=("none", "bead", "residue"), default=argparse.SUPPRESS,
                    help="contacts between atoms (none), beads of the run's mapping, or residues of a peptide (none)")
+    p.add_argument("--flex_stats", action="store_true", default=argparse.SUPPRESS,
+                   help="mean structure and per-atom fluctuation (RMSF) of the output against -ref; writes flex_stats.json next to -out")
+    p.add_argument("-flex_atoms", choices=("heavy", "all"), default=argparse.SUPPRESS,
+                   help="atoms that --flex_stats superposes and reports (heavy)")
+    p.add_argument("-flex_groups", choices=("none", "bead", "residue"), default=argparse.SUPPRESS,
+                   help="a profile row per atom (none), per bead of the run's mapping, or per residue of a peptide (none)")
+    p.add_argument("-flex_aligned", type=str, default=argparse.SUPPRESS,
+                   help="with --flex_stats: also write the output structures in their mean's frame, and the mean, to this .npz")
     return p
 
 
@@ -327,6 +345,14 @@ CONTACT_DEFAULTS = {"contact_stats": False, "contact_cutoff": 4.5, "contact_atom
 def contact_args(args) -> dict:
     """The ``--contact_stats`` switches of parsed arguments, with their defaults where they were not given."""
     return {k: getattr(args, k, v) for k, v in CONTACT_DEFAULTS.items()}
+
+
+FLEX_DEFAULTS = {"flex_stats": False, "flex_atoms": "heavy", "flex_groups": "none", "flex_aligned": None}
+
+
+def flex_args(args) -> dict:
+    """The ``--flex_stats`` switches of parsed arguments, with their defaults where they were not given."""
+    return {k: getattr(args, k, v) for k, v in FLEX_DEFAULTS.items()}
 
 
 def _npz(path: str, need) -> dict:
@@ -347,10 +373,12 @@ def read_inputs(args, params, device=None) -> dict:
     z = bonds = ref_xyz = None
     dist_stats, tica_stats = getattr(args, "dist_stats", False), getattr(args, "tica_stats", False)
     cov_stats = getattr(args, "cov_stats", False)
-    contact = contact_args(args)
-    need_ref, starts = dist_stats or tica_stats or cov_stats or contact["contact_stats"], None
+    contact, flex = contact_args(args), flex_args(args)
+    if not flex["flex_stats"] and any(getattr(args, k, None) is not None for k in ("flex_atoms", "flex_groups", "flex_aligned")):
+        raise SystemExit("-flex_atoms / -flex_groups / -flex_aligned are options of --flex_stats")
+    need_ref, starts = dist_stats or tica_stats or cov_stats or contact["contact_stats"] or flex["flex_stats"], None
     if getattr(args, "ref", None) and not need_ref:
-        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats / --contact_stats")
+        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats / --contact_stats / --flex_stats")
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
@@ -378,7 +406,8 @@ def read_inputs(args, params, device=None) -> dict:
     if args.require_valid and bonds is None:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
     if need_ref:
-        switch = "--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats" if cov_stats else "--contact_stats"
+        switch = ("--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats" if cov_stats else
+                  "--contact_stats" if contact["contact_stats"] else "--flex_stats")
         if bonds is None:
             raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
@@ -418,6 +447,15 @@ def read_inputs(args, params, device=None) -> dict:
                     contacts.groups_of(z, bonds, None, "residue")
                 except ValueError as err:
                     raise SystemExit(f"--contact_stats: {err}")
+        if flex["flex_stats"]:
+            from . import contacts, coverage
+            if coverage.select_atoms(z, flex["flex_atoms"]).shape[0] < 3:
+                raise SystemExit(f"--flex_stats: the topology has fewer than three {flex['flex_atoms']} atoms: no rotation to fit")
+            if flex["flex_groups"] == "residue":
+                try:
+                    contacts.groups_of(z, bonds, None, "residue")
+                except ValueError as err:
+                    raise SystemExit(f"--flex_stats: {err}")
     if params.get("cg_radius_graph") and bonds is None:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
     return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if need_ref else {}),
@@ -495,6 +533,23 @@ def run(args) -> dict:
         with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "contact_stats.json"), "w") as f:
             json.dump(stats, f)
         dist["contact_stats"] = contacts.summary_of(stats)
+    flex = flex_args(args)
+    if flex["flex_stats"]:
+        from . import coverage, flexibility
+        gen = res["xyz"].reshape(T * K, -1, 3)
+        stats = flexibility.compare(inp["ref_xyz"], gen, z, bonds, atoms=flex["flex_atoms"],
+                                    groups=None if flex["flex_groups"] == "none" else flex["flex_groups"], mapping=mapping,
+                                    device=device)
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "flex_stats.json"), "w") as f:
+            json.dump(stats, f)
+        dist["flex_stats"] = flexibility.summary_of(stats)
+        if flex["flex_aligned"]:
+            sel = coverage.select_atoms(z, flex["flex_atoms"])
+            own = flexibility.mean_structure(gen, sel, device=device)
+            if own["mean"] is None:
+                raise SystemExit("-flex_aligned: no output structure is finite, there is no mean to align to")
+            np.savez_compressed(flex["flex_aligned"], xyz=flexibility.aligned(gen, own["mean"], sel, device=device), mean=own["mean"],
+                                rmsf=own["rmsf"], atoms=sel.astype(np.int64))
 
     def mean(key):
         if key not in res:

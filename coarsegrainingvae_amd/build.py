@@ -26,11 +26,12 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # (csrc/sq_dist.h) against host-derived thresholds -- no product may fuse into a sum there; the histogram kernel's fp64
 # path from coordinates to bin index is restated on the host operation for operation; the TICA kernels' fp32 distances
 # are restated in numpy.float32 bit for bit; the two forms of the betweenness kernel and of the baseline trainer must
-# round alike; the contact kernels test sq_dist2 against a cutoff that the host restates bit for bit
+# round alike; the contact kernels test sq_dist2 against a cutoff that the host restates bit for bit; the alignment
+# kernel's rotation solve (csrc/superpose_rot.h) is the text a host program compiles to measure it against LAPACK
 SOURCE_FLAGS = {"newman.hip": ["-ffp-contract=off"], "baseline.hip": ["-ffp-contract=off"],
                 "sample_quality.hip": ["-ffp-contract=off"], "ensemble_check.hip": ["-ffp-contract=off"],
                 "internal_hist.hip": ["-ffp-contract=off"], "tica.hip": ["-ffp-contract=off"],
-                "contact_map.hip": ["-ffp-contract=off"]}
+                "contact_map.hip": ["-ffp-contract=off"], "align_mean.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

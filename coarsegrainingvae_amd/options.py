@@ -36,6 +36,7 @@ HOST = {
     "cgae_form": 0,         # mapping learner (cgmap.py): 0 rule of cgv_cgae_resident_fits (state in one workgroup's LDS when n_atoms x n_cgs fits), 1 resident, 2 streamed (tests force either at a small size)
     "newman_form": 0,       # Girvan-Newman partition (cgmap.partition_newman): 0 rule of cgv_newman_resident_fits (a workgroup's per-source state in LDS when n_atoms / n_edges fit), 1 resident, 2 streamed (tests force either at a small size)
     "baseline_form": 0,     # linear baselines (baseline.py): 0 rule of cgv_baseline_resident_fits (matrix and Adam moments in one workgroup's LDS when they fit), 1 resident, 2 global (tests force either at a small size)
+    "align_form": 0,        # mean structure / RMSF (flexibility.py): 0 rule of cgv_align_wave_fits (a wave owns a structure up to 256 atoms, a block of 256 threads beyond), 1 wave, 2 block (tests force either at a small size)
     "decoder_dense": 0,     # full-width products of the fused decoder loop: 0 four-column blocks (cgv_decoder_dense_fwd), 1 skinny_fwd_k
 }
 _DEFAULTS = dict(HOST)

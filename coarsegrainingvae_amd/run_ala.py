@@ -124,6 +124,9 @@ def build_extras_parser() -> argparse.ArgumentParser:
     p.add_argument("--contact_eval", action="store_true", default=argparse.SUPPRESS,
                    help="after the evaluation, heavy-atom contact maps, native contacts and Rg of the hold-out frames' prior "
                         "samples against those frames (contacts.compare): contact_stats.json in the log directory")
+    p.add_argument("--flex_eval", action="store_true", default=argparse.SUPPRESS,
+                   help="after the evaluation, mean structure and per-atom fluctuation (RMSF) of the hold-out frames' prior "
+                        "samples against those frames (flexibility.compare): flex_stats.json in the log directory")
     return p
 
 
@@ -131,7 +134,7 @@ def stored_params(params: dict) -> dict:
     """What ``modelparams.json`` records of the parameters: a switch of ``build_extras_parser`` that is off leaves the
     file as it was before the switch existed (its key, and the keys of its options, are left out)."""
     off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"),
-                               ("cov_eval", "cov_eval"), ("contact_eval", "contact_eval"))
+                               ("cov_eval", "cov_eval"), ("contact_eval", "contact_eval"), ("flex_eval", "flex_eval"))
            if not params.get(switch)]
     return {k: v for k, v in params.items() if k not in off}
 
@@ -306,6 +309,8 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
         stats["cov_stats"] = cov_eval(dataset, val_idx, samples, device, logdir)
     if params.get("contact_eval"):
         stats["contact_stats"] = contact_eval(dataset, val_idx, samples, device, logdir)
+    if params.get("flex_eval"):
+        stats["flex_stats"] = flex_eval(dataset, val_idx, samples, device, logdir)
     return stats
 
 
@@ -363,6 +368,28 @@ def contact_eval(dataset, val_idx, samples, device, logdir):
         with open(os.path.join(logdir, "contact_stats.json"), "w") as f:
             json.dump(full, f)
     return contacts.summary_of(full)
+
+
+def flex_eval(dataset, val_idx, samples, device, logdir):
+    """``--flex_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
+    tuple) by the fluctuation of their heavy atoms about each set's own mean structure.  Writes ``flex_stats.json``;
+    returns ``flexibility.summary_of``, which stays in the summary's ``"test_stats"``, or ``None`` when there is nothing to
+    compare (fewer than two hold-out frames, frames of different molecules, or fewer than three atoms)."""
+    from . import flexibility
+    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
+        print("--flex_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
+        return None
+    frame = dataset[val_idx[0]]
+    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
+    atoms = "heavy" if (z != 1).sum() >= 3 else "all"
+    if n < 3:
+        print("--flex_eval skipped: fewer than three atoms, no rotation to fit", file=sys.stderr, flush=True)
+        return None
+    full = flexibility.compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy(), atoms=atoms, device=device)
+    if logdir:
+        with open(os.path.join(logdir, "flex_stats.json"), "w") as f:
+            json.dump(full, f)
+    return flexibility.summary_of(full)
 
 
 def tica_eval(params, dataset, val_idx, samples, device, logdir):

@@ -1223,6 +1223,43 @@ int cgv_contact_group_counts(const float* xyz, const int32_t* sel /*[m]*/, const
                              int32_t* n_native, double* rg2 /*or NULL*/, int32_t* bad, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K21  superpose an ensemble onto a target and accumulate its mean structure and per-atom fluctuation (RMSF) -- how much
+ * an ensemble moves.  Nothing in the reference superposes anything.
+ *   xyz [n_structures,n_atoms,3] fp32         the structures
+ *   sel [m] int32, 1 <= m <= n_atoms          the atoms the superposition is fitted on.  An index outside [0, n_atoms) is
+ *                                             ignored and an atom named twice counts once (the host wrapper refuses both).
+ *   ref [n_atoms,3] fp64                      the target
+ * Per structure: structure and target are centred on the centroid of their selected atoms; M = sum over sel of a~^T b~ in
+ * fp64 on exactly widened coordinates; the PROPER rotation R that maximises sum b~ . R a~ from the eigenvector of the
+ * largest eigenvalue of the quaternion key matrix (csrc/superpose_rot.h: the Jacobi sweeps of K17 with the rotations
+ * accumulated, a deterministic rule for the sign and inside a degenerate eigenspace; a mirror image is never a solution);
+ * y = R a~ for EVERY atom.  The call MERGES (adds) into the caller's accumulators, so a caller may chunk:
+ *   sum [n_atoms,3] fp64                      += y of every good structure (the centred frame of the target)
+ *   dev2 [n_atoms] fp64                       += |y - b~|^2
+ *   n_good [1] int32                          += structures that are not bad
+ * and overwrites, per structure,
+ *   rmsd2 [n_structures] fp64                 max(0, G_a + G_b - 2 lambda) / m over the selection; NaN for a bad structure
+ *   bad [n_structures] int32                  1 when ANY coordinate of the structure is not finite: it contributes nothing
+ *   aligned [n_structures,n_atoms,3] fp32     (may be NULL) y, rounded; NaN for a bad structure
+ * form: 0 the rule (cgv_align_wave_fits(n_atoms): a wave owns a structure, else a block of 256 threads does), 1 / 2 force
+ * either.  Two launches: groups of threads own contiguous ranges of structures (at least 4; as many ranges as bring the
+ * grid to 4096 waves / 512 blocks), a thread owns atoms and keeps their accumulators in registers, the selection is a bit
+ * mask in LDS so every structure is read once; reductions are fixed trees; a second launch adds the ranges' partial sums
+ * in ascending order.  No [S,n,3] fp64 intermediate, no floating-point atomics: the order of every addition is a function
+ * of (n_structures, n_atoms, m, form) alone -- the same bits on every run.
+ * workspace: cgv_align_workspace_bytes(n_structures, n_atoms, form) bytes, 8-byte aligned, contents need not survive.
+ * Limits: n_atoms <= cgv_align_max_atoms(), n_structures <= cgv_align_max_structures() per launch; beyond a limit the call
+ * fails (CGV_E_BADARG) before any launch.  Bound: see DESIGN.md (K21 row). */
+int cgv_align_max_atoms(void);
+int cgv_align_max_structures(void);
+int cgv_align_wave_fits(int n_atoms);
+size_t cgv_align_workspace_bytes(int n_structures, int n_atoms, int form);
+int cgv_align_accumulate(const float* xyz, const int32_t* sel /*[m]*/, const double* ref /*[n_atoms,3]*/, int n_structures,
+                         int n_atoms, int m, int form, double* sum /*[n_atoms,3]*/, double* dev2 /*[n_atoms]*/, int32_t* n_good,
+                         double* rmsd2, int32_t* bad, float* aligned /*or NULL*/, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
