@@ -204,6 +204,14 @@ PROTOTYPES = {
     "cgv_internal_hist_feature_tile": (_i, [_i]),
     "cgv_internal_hist_pair_tile": (_i, [_i]),
     "cgv_internal_hist": (_i, [_p] * 4 + [_i] * 6 + [C.c_double] * 2 + [_p] * 3),
+    "cgv_internal_values": (_i, [_p] * 3 + [_i] * 3 + [_p] * 3),
+    "cgv_kde_max_planes": (_i, []),
+    "cgv_kde_max_samples": (_i, []),
+    "cgv_kde_max_points": (_i, []),
+    "cgv_kde_max_splits": (_i, []),
+    "cgv_kde_splits": (_i, [_i, _i, _i]),
+    "cgv_kde_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_kde_sums": (_i, [_p] * 3 + [_i] * 5 + [_p, _p, _p, _sz, _p]),
     "cgv_tica_max_features": (_i, []),
     "cgv_tica_max_atoms": (_i, []),
     "cgv_tica_max_bins2": (_i, []),

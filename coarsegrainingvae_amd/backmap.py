@@ -20,6 +20,7 @@ launches K14 (``cgv_ensemble_check``) ONCE and reads everything back ONCE.  No a
         [--contact_stats [-contact_cutoff 4.5] [-contact_atoms heavy|all] [-contact_exclude 3]
          [-contact_groups none|bead|residue]]
         [--flex_stats [-flex_atoms heavy|all] [-flex_groups none|bead|residue] [-flex_aligned aligned.npz]]
+        [--kde_stats [-kde_plane torsion|tica] [-kde_grid 100] [-kde_bw scott|silverman|<float>]]
 
 ``-cg``: ``cg_xyz [T,N,3]`` in Angstrom.  ``-traj``: a ``tools/traj_to_npz.py`` file; its beads are the ``scatter_mean`` of
 the atoms over the run's mapping (no rotation) -- the "coarse-grain, then backmap" round trip -- and its ``z`` / ``bonds``
@@ -63,6 +64,14 @@ floor of the reference: ``flex_stats.json`` next to ``-out``, the short form int
 ``"flex_stats"``.  ``-flex_aligned file.npz`` also writes the backmapped structures in their mean's frame (``xyz``
 [T*K,n,3]), the mean (``mean``), ``rmsf`` and the selection (``atoms``).  Needs a topology.  These switches, too, are
 absent from the parsed arguments unless given.
+
+``--kde_stats``: do the backmapped structures have the free-energy surface of the reference?  ``density.compare_torsions``
+(``-kde_plane torsion``: every (phi, psi) plane of the backbone) or ``density.compare_tica`` (``tica``: the reference's
+(IC1, IC2) plane at ``-tica_lag``): Gaussian kernel density estimates (K22) of all ``T * K`` structures and of the frames
+of ``-ref`` on ``-kde_grid`` nodes per axis with bandwidth ``-kde_bw``, their Jensen-Shannon divergence, the RMS
+difference of their free energies and the mean log density of the structures under the reference's estimate, with the
+even / odd floor of the reference: ``kde_stats.json`` next to ``-out``, the short form into the summary line under
+``"kde_stats"``.  Needs a topology with a peptide backbone and at least four reference frames.  Absent unless given.
 """
 from __future__ import annotations
 
@@ -335,6 +344,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="a profile row per atom (none), per bead of the run's mapping, or per residue of a peptide (none)")
     p.add_argument("-flex_aligned", type=str, default=argparse.SUPPRESS,
                    help="with --flex_stats: also write the output structures in their mean's frame, and the mean, to this .npz")
+    p.add_argument("--kde_stats", action="store_true", default=argparse.SUPPRESS,
+                   help="kernel density estimates (free-energy surfaces) of the output against -ref in the backbone-torsion or "
+                        "TICA plane; writes kde_stats.json next to -out")
+    p.add_argument("-kde_plane", choices=("torsion", "tica"), default=argparse.SUPPRESS,
+                   help="plane of --kde_stats: every (phi, psi) pair, or (IC1, IC2) with -tica_lag (torsion)")
+    p.add_argument("-kde_grid", type=int, default=argparse.SUPPRESS, help="grid nodes per axis of --kde_stats (100)")
+    p.add_argument("-kde_bw", type=kde_bandwidth, default=argparse.SUPPRESS,
+                   help="bandwidth of --kde_stats: scott, silverman or a positive factor (scott)")
     return p
 
 
@@ -353,6 +370,27 @@ FLEX_DEFAULTS = {"flex_stats": False, "flex_atoms": "heavy", "flex_groups": "non
 def flex_args(args) -> dict:
     """The ``--flex_stats`` switches of parsed arguments, with their defaults where they were not given."""
     return {k: getattr(args, k, v) for k, v in FLEX_DEFAULTS.items()}
+
+
+KDE_DEFAULTS = {"kde_stats": False, "kde_plane": "torsion", "kde_grid": 100, "kde_bw": "scott"}
+
+
+def kde_bandwidth(text: str):
+    """``-kde_bw``: ``scott``, ``silverman`` or a positive number."""
+    if text in ("scott", "silverman"):
+        return text
+    try:
+        value = float(text)
+    except ValueError:
+        value = -1.0
+    if not (value > 0 and np.isfinite(value)):
+        raise argparse.ArgumentTypeError("scott, silverman or a positive number")
+    return value
+
+
+def kde_args(args) -> dict:
+    """The ``--kde_stats`` switches of parsed arguments, with their defaults where they were not given."""
+    return {k: getattr(args, k, v) for k, v in KDE_DEFAULTS.items()}
 
 
 def _npz(path: str, need) -> dict:
@@ -376,9 +414,13 @@ def read_inputs(args, params, device=None) -> dict:
     contact, flex = contact_args(args), flex_args(args)
     if not flex["flex_stats"] and any(getattr(args, k, None) is not None for k in ("flex_atoms", "flex_groups", "flex_aligned")):
         raise SystemExit("-flex_atoms / -flex_groups / -flex_aligned are options of --flex_stats")
-    need_ref, starts = dist_stats or tica_stats or cov_stats or contact["contact_stats"] or flex["flex_stats"], None
+    kde = kde_args(args)
+    if not kde["kde_stats"] and any(getattr(args, k, None) is not None for k in ("kde_plane", "kde_grid", "kde_bw")):
+        raise SystemExit("-kde_plane / -kde_grid / -kde_bw are options of --kde_stats")
+    kde_tica = kde["kde_stats"] and kde["kde_plane"] == "tica"
+    need_ref, starts = dist_stats or tica_stats or cov_stats or contact["contact_stats"] or flex["flex_stats"] or kde["kde_stats"], None
     if getattr(args, "ref", None) and not need_ref:
-        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats / --contact_stats / --flex_stats")
+        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats / --contact_stats / --flex_stats / --kde_stats")
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
@@ -407,7 +449,7 @@ def read_inputs(args, params, device=None) -> dict:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
     if need_ref:
         switch = ("--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats" if cov_stats else
-                  "--contact_stats" if contact["contact_stats"] else "--flex_stats")
+                  "--contact_stats" if contact["contact_stats"] else "--flex_stats" if flex["flex_stats"] else "--kde_stats")
         if bonds is None:
             raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
@@ -419,17 +461,17 @@ def read_inputs(args, params, device=None) -> dict:
                 raise SystemExit(f"{args.ref}: z differs from the topology's (the reference must list the same atoms in the same order)")
         if ref_xyz is None or ref_xyz.shape[0] < 2:
             raise SystemExit(f"{switch} needs reference frames: -ref file.npz (or -traj as the source), at least two")
-        if tica_stats:
+        if tica_stats or kde_tica:
             from . import tica
             if args.tica_lag < 1 or ref_xyz.shape[0] < args.tica_lag + 2:
-                raise SystemExit(f"--tica_stats needs 1 <= -tica_lag and at least lag + 2 reference frames: {ref_xyz.shape[0]} "
+                raise SystemExit(f"{'--tica_stats' if tica_stats else '--kde_stats -kde_plane tica'} needs 1 <= -tica_lag and at least lag + 2 reference frames: {ref_xyz.shape[0]} "
                                  f"frames, lag {args.tica_lag}")
             if tica.backbone_atoms(z, bonds).shape[0] == 0:
-                raise SystemExit("--tica_stats: the topology has no peptide backbone to take the distances from")
+                raise SystemExit(f"{'--tica_stats' if tica_stats else '--kde_stats'}: the topology has no peptide backbone to take the distances from")
             try:
                 tica.split_segments(ref_xyz, starts)
             except ValueError as err:
-                raise SystemExit(f"--tica_stats: {err}")
+                raise SystemExit(f"{'--tica_stats' if tica_stats else '--kde_stats'}: {err}")
         if cov_stats:
             from . import coverage
             if not args.cov_thresholds or min(args.cov_thresholds) <= 0:
@@ -456,10 +498,18 @@ def read_inputs(args, params, device=None) -> dict:
                     contacts.groups_of(z, bonds, None, "residue")
                 except ValueError as err:
                     raise SystemExit(f"--flex_stats: {err}")
+        if kde["kde_stats"]:
+            from . import distributions
+            if kde["kde_grid"] < 2:
+                raise SystemExit("--kde_stats: -kde_grid must be at least 2 nodes per axis")
+            if ref_xyz.shape[0] < 4:
+                raise SystemExit("--kde_stats needs at least four reference frames (its floor compares the even with the odd ones)")
+            if kde["kde_plane"] == "torsion" and not distributions.peptide_backbone_torsions(z, bonds)[2]:
+                raise SystemExit("--kde_stats: the topology has no peptide backbone, so no (phi, psi) plane")
     if params.get("cg_radius_graph") and bonds is None:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
     return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if need_ref else {}),
-            **({"ref_starts": starts} if tica_stats else {})}
+            **({"ref_starts": starts} if tica_stats or kde_tica else {})}
 
 
 def run(args) -> dict:
@@ -550,6 +600,21 @@ def run(args) -> dict:
                 raise SystemExit("-flex_aligned: no output structure is finite, there is no mean to align to")
             np.savez_compressed(flex["flex_aligned"], xyz=flexibility.aligned(gen, own["mean"], sel, device=device), mean=own["mean"],
                                 rmsf=own["rmsf"], atoms=sel.astype(np.int64))
+    kde = kde_args(args)
+    if kde["kde_stats"]:
+        from . import density, tica
+        gen = res["xyz"].reshape(T * K, -1, 3)
+        try:
+            if kde["kde_plane"] == "torsion":
+                stats = density.compare_torsions(inp["ref_xyz"], gen, z, bonds, n_grid=kde["kde_grid"], bandwidth=kde["kde_bw"], device=device)
+            else:
+                stats = density.compare_tica(tica.split_segments(inp["ref_xyz"], inp["ref_starts"]), gen, z, bonds, lag=args.tica_lag,
+                                             n_grid=kde["kde_grid"], bandwidth=kde["kde_bw"], device=device)
+        except ValueError as err:
+            raise SystemExit(f"--kde_stats: {err}")
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "kde_stats.json"), "w") as f:
+            json.dump(stats, f)
+        dist["kde_stats"] = density.summary_of(stats)
 
     def mean(key):
         if key not in res:

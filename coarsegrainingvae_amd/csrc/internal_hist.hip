@@ -248,3 +248,53 @@ int cgv_internal_hist(const float* xyz, const int32_t* feat, const int32_t* kind
 }
 
 }  // extern "C"
+
+// ----------------------------------------------------------------------------- the values themselves (cgv_internal_values)
+// What K15 bins, written out: values [S, Nf] fp64 through the same ih_value, one thread per (structure, feature) item,
+// adjacent lanes on adjacent features of one structure, the 2 .. 4 atoms gathered from global memory.  An invalid item is
+// NaN and counts once in n_invalid (an integer atomic per wave that has any: exact in any order).  Bound: as K15, the
+// fp64 atan2 / sqrt of the items.
+namespace cgv {
+
+constexpr long long IV_MAX_ITEMS = 1ll << 36;            // structures x features of a launch
+
+__global__ __launch_bounds__(IH_THREADS) void internal_values_k(const float* __restrict__ xyz, const int* __restrict__ feat,
+                                                                const int* __restrict__ kind, long long items, int n, int Nf,
+                                                                double* __restrict__ values, int* __restrict__ n_invalid) {
+  const long long it = (long long)blockIdx.x * IH_THREADS + threadIdx.x;
+  bool invalid = false;
+  if (it < items) {
+    const long long s = it / Nf;
+    const int f = (int)(it - s * Nf);
+    int rec[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) rec[a] = feat[4 * (size_t)f + a];
+    double val;
+    invalid = !ih_value(xyz + 3 * (size_t)n * (size_t)s, n, rec, kind[f], val);
+    values[it] = invalid ? (double)NAN : val;
+  }
+  const unsigned long long any = __ballot(invalid);
+  if (any != 0ull && (threadIdx.x & 63) == 0) atomicAdd(n_invalid, (int)__popcll(any));
+}
+
+}  // namespace cgv
+
+extern "C" {
+
+int cgv_internal_values(const float* xyz, const int32_t* feat, const int32_t* kind, int n_structures, int n_atoms, int n_features,
+                        double* values, int32_t* n_invalid, void* stream) {
+  CGV_REQUIRE(n_structures >= 0 && n_atoms >= 0 && n_features >= 0, "bad size");
+  CGV_REQUIRE(n_features <= cgv::IH_MAX_FEATURES, "n_features <= cgv_internal_hist_max_features()");
+  CGV_REQUIRE(n_atoms <= cgv::IH_MAX_ATOMS, "n_atoms <= cgv_internal_hist_max_atoms()");
+  const long long items = (long long)n_structures * n_features;
+  CGV_REQUIRE(items <= cgv::IV_MAX_ITEMS, "n_structures * n_features <= 2^36 per launch");
+  if (items == 0) return 0;
+  CGV_REQUIRE(feat && kind && values && n_invalid, "null pointer");
+  CGV_REQUIRE(n_atoms >= 1 && xyz, "features of a structure without atoms (ih_value reads atom 0 of it)");
+  const unsigned blocks = (unsigned)((items + cgv::IH_THREADS - 1) / cgv::IH_THREADS);
+  hipLaunchKernelGGL(cgv::internal_values_k, dim3(blocks), dim3(cgv::IH_THREADS), 0, (hipStream_t)stream, xyz, feat, kind, items,
+                     n_atoms, n_features, values, n_invalid);
+  return cgv::check_launch("cgv_internal_values");
+}
+
+}  // extern "C"

@@ -215,8 +215,57 @@ def histograms(xyz, coords: InternalCoords, n_bins: int = 36, n_bins2: int = 36,
     return {"counts": counts, "pair_counts": pair_counts}
 
 
+def internal_values(xyz: torch.Tensor, table: _DeviceTable, values: torch.Tensor, n_invalid: torch.Tensor) -> None:
+    """One ``cgv_internal_values`` launch: the features of ``xyz [S,n,3]`` (device, fp32) are written to ``values [S,Nf]``
+    (device, fp64; NaN: invalid), and the invalid items are ADDED to ``n_invalid [1]`` (device, int32)."""
+    S, n = int(xyz.shape[0]), int(xyz.shape[1])
+    if tuple(values.shape) != (S, table.n_features) or values.dtype != torch.float64 or xyz.dtype != torch.float32:
+        raise ValueError("xyz must be float32 and values float64 [structures, features]")
+    if tuple(n_invalid.shape) != (1,) or n_invalid.dtype != torch.int32:
+        raise ValueError("n_invalid must be int32 [1]")
+    if S == 0 or table.n_features == 0:
+        return
+    _lib.call("cgv_internal_values", _lib.ptr(xyz), _lib.ptr(table.feat), _lib.ptr(table.kind), S, n, table.n_features,
+              _lib.ptr(values), _lib.ptr(n_invalid), _lib.stream_ptr(), tag="internal_values")
+
+
+def feature_values(xyz, coords: InternalCoords, rows=None, structures_per_launch: int = 16384, device="cuda",
+                   return_invalid: bool = False):
+    """The internal coordinates themselves: ``values [S, F]`` (host, fp64) of the structures ``xyz [S,n,3]`` (a host
+    array, or a tensor on any device -- a device tensor decides the device) for the rows ``rows`` of ``coords`` (default:
+    all, ``F = Nf``), computed by the device function that K15 bins with.  An invalid item (a non-finite coordinate, an
+    atom outside the structure) is NaN; ``return_invalid=True`` also returns their number.  One launch per
+    ``structures_per_launch`` structures, ONE read-back."""
+    from .evaluate import _read_back
+    lim = limits()
+    sub = coords
+    if rows is not None:
+        r = np.asarray(rows, dtype=np.int64).reshape(-1)
+        if r.shape[0] and (r.min() < 0 or r.max() >= coords.n_features):
+            raise ValueError(f"rows name feature {int(r.max() if r.max() >= coords.n_features else r.min())}, the table has {coords.n_features}")
+        sub = InternalCoords(np.ascontiguousarray(coords.feat[r]), np.ascontiguousarray(coords.kind[r]), np.zeros((0, 2), np.int32),
+                             coords.n_atoms)
+    if sub.n_features > lim["features"]:
+        raise ValueError(f"{sub.n_features} features in one launch (the kernel holds {lim['features']})")
+    x = xyz if torch.is_tensor(xyz) else torch.from_numpy(np.ascontiguousarray(np.asarray(xyz, dtype=np.float32)))
+    if x.dim() != 3 or x.shape[2] != 3 or int(x.shape[1]) != coords.n_atoms:
+        raise ValueError(f"xyz must be [structures, {coords.n_atoms}, 3], got {tuple(x.shape)}")
+    if not 1 <= coords.n_atoms <= lim["atoms"]:
+        raise ValueError(f"{coords.n_atoms} atoms per structure (the kernel holds 1..{lim['atoms']})")
+    dev = x.device if x.is_cuda else torch.device(device)
+    M = max(int(structures_per_launch), 1)
+    table = _DeviceTable(sub, dev)
+    values = torch.empty((int(x.shape[0]), sub.n_features), dtype=torch.float64, device=dev)
+    n_invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+    for start in range(0, int(x.shape[0]), M):
+        chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+        internal_values(chunk, table, values[start:start + M], n_invalid)
+    out, bad = _read_back([values, n_invalid])
+    return (out, int(bad[0])) if return_invalid else out
+
+
 # ----------------------------------------------------------------------------- host statistics
-UNDER, OVER, INVALID = 0, -2, -1          # slots of a feature's row next to its bins [1 : -2]
+UNDER, OVER, INVALID = 0, -2, -1         # slots of a feature's row next to its bins [1 : -2]
 
 
 def js_divergence(counts_a, counts_b) -> Optional[float]:

@@ -37,7 +37,8 @@ HOST = {
     "newman_form": 0,       # Girvan-Newman partition (cgmap.partition_newman): 0 rule of cgv_newman_resident_fits (a workgroup's per-source state in LDS when n_atoms / n_edges fit), 1 resident, 2 streamed (tests force either at a small size)
     "baseline_form": 0,     # linear baselines (baseline.py): 0 rule of cgv_baseline_resident_fits (matrix and Adam moments in one workgroup's LDS when they fit), 1 resident, 2 global (tests force either at a small size)
     "align_form": 0,        # mean structure / RMSF (flexibility.py): 0 rule of cgv_align_wave_fits (a wave owns a structure up to 256 atoms, a block of 256 threads beyond), 1 wave, 2 block (tests force either at a small size)
-    "decoder_dense": 0,     # full-width products of the fused decoder loop: 0 four-column blocks (cgv_decoder_dense_fwd), 1 skinny_fwd_k
+    "kde_splits": 0,        # kernel density sums (density.py): sample ranges of a cgv_kde_sums launch, 0 rule of cgv_kde_splits (a function of planes, samples and points alone), 1 .. cgv_kde_max_splits() (tests force 1, 2 or 7 at a small size)
+    "decoder_dense": 0,    # full-width products of the fused decoder loop: 0 four-column blocks (cgv_decoder_dense_fwd), 1 skinny_fwd_k
 }
 _DEFAULTS = dict(HOST)
 

@@ -127,6 +127,9 @@ def build_extras_parser() -> argparse.ArgumentParser:
     p.add_argument("--flex_eval", action="store_true", default=argparse.SUPPRESS,
                    help="after the evaluation, mean structure and per-atom fluctuation (RMSF) of the hold-out frames' prior "
                         "samples against those frames (flexibility.compare): flex_stats.json in the log directory")
+    p.add_argument("--kde_eval", action="store_true", default=argparse.SUPPRESS,
+                   help="after the evaluation, kernel density estimates of the hold-out frames and their prior samples in every "
+                        "(phi, psi) plane (density.compare_torsions): kde_stats.json in the log directory")
     return p
 
 
@@ -134,7 +137,8 @@ def stored_params(params: dict) -> dict:
     """What ``modelparams.json`` records of the parameters: a switch of ``build_extras_parser`` that is off leaves the
     file as it was before the switch existed (its key, and the keys of its options, are left out)."""
     off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"),
-                               ("cov_eval", "cov_eval"), ("contact_eval", "contact_eval"), ("flex_eval", "flex_eval"))
+                               ("cov_eval", "cov_eval"), ("contact_eval", "contact_eval"), ("flex_eval", "flex_eval"),
+                               ("kde_eval", "kde_eval"))
            if not params.get(switch)]
     return {k: v for k, v in params.items() if k not in off}
 
@@ -311,6 +315,8 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
         stats["contact_stats"] = contact_eval(dataset, val_idx, samples, device, logdir)
     if params.get("flex_eval"):
         stats["flex_stats"] = flex_eval(dataset, val_idx, samples, device, logdir)
+    if params.get("kde_eval"):
+        stats["kde_stats"] = kde_eval(dataset, val_idx, samples, device, logdir)
     return stats
 
 
@@ -390,6 +396,32 @@ def flex_eval(dataset, val_idx, samples, device, logdir):
         with open(os.path.join(logdir, "flex_stats.json"), "w") as f:
             json.dump(full, f)
     return flexibility.summary_of(full)
+
+
+def kde_eval(dataset, val_idx, samples, device, logdir):
+    """``--kde_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
+    tuple) as kernel density estimates in every (phi, psi) plane of the backbone.  Writes ``kde_stats.json``; returns
+    ``density.summary_of``, which stays in the summary's ``"test_stats"``, or ``None`` when there is nothing to compare
+    (where ``--dist_eval`` has nothing, fewer than four hold-out frames, or a molecule without a peptide backbone)."""
+    from . import density, distributions
+    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 4:
+        print("--kde_eval skipped: it needs at least four hold-out frames of one molecule", file=sys.stderr, flush=True)
+        return None
+    frame = dataset[val_idx[0]]
+    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
+    bonds = frame["bond_edge_list"].numpy()
+    if not distributions.peptide_backbone_torsions(z, bonds)[2]:
+        print("--kde_eval skipped: the molecule has no peptide backbone, so no (phi, psi) plane", file=sys.stderr, flush=True)
+        return None
+    try:
+        full = density.compare_torsions(samples[1], samples[0].reshape(-1, n, 3), z, bonds, device=device)
+    except ValueError as err:                                            # a torsion without spread, a kernel wider than period / 12
+        print(f"--kde_eval skipped: {err}", file=sys.stderr, flush=True)
+        return None
+    if logdir:
+        with open(os.path.join(logdir, "kde_stats.json"), "w") as f:
+            json.dump(full, f)
+    return density.summary_of(full)
 
 
 def tica_eval(params, dataset, val_idx, samples, device, logdir):

@@ -1260,6 +1260,44 @@ int cgv_align_accumulate(const float* xyz, const int32_t* sel /*[m]*/, const dou
                          double* rmsd2, int32_t* bad, float* aligned /*or NULL*/, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K15b  the internal-coordinate VALUES that K15 bins: values [n_structures,n_features] fp64 of the feature records
+ * (feat, kind: as cgv_internal_hist), through the same device function and the same operation order (no FMA contraction).
+ * An invalid item (K15's rule) is written as NaN and ADDS one to n_invalid [1] int32 (zeroed by the caller).  One launch,
+ * one thread per item.  Limits: n_features / n_atoms as K15, n_atoms >= 1, n_structures * n_features <= 2^36. */
+int cgv_internal_values(const float* xyz, const int32_t* feat /*[n_features,4]*/, const int32_t* kind /*[n_features]*/,
+                        int n_structures, int n_atoms, int n_features, double* values, int32_t* n_invalid, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * K22  the sums of a Gaussian kernel density estimate -- the numbers behind the reference's kernel_density_plot
+ * (CoarseGrainingVAE/plots.py:61-84: scipy.stats.gaussian_kde on a 300 x 300 grid).  For n_planes independent planes:
+ *   samples [n_planes,n_samples,d] fp32, points [n_planes,n_points,d] fp32, d = 1 or 2
+ *   period  [n_planes,d] fp32 or NULL         0 (or less): the axis is not periodic.  NULL: no axis of any plane is.
+ *   sums    [n_planes,n_points] fp64          sums[p,m] = sum_i exp2(-|points[p,m] - samples[p,i]|^2), OVERWRITTEN
+ *   n_skipped [n_planes] int32                non-finite samples of the plane (they add no term), OVERWRITTEN
+ * On a periodic axis a difference is reduced to its minimum image, delta - period * rint(delta * (1 / period)), before
+ * squaring.  The caller has centred, whitened and scaled the coordinates by sqrt(log2(e) / 2): the kernel knows nothing
+ * of bandwidths.  fp32 differences, squares and v_exp_f32 of 64 - |delta|^2, scaled back by 2^-64 in fp64 at the end
+ * (terms with |delta|^2 > 190 are flushed to zero: nothing that counts in a sum of N 2^-126 or more); a point's
+ * terms are added in fp32 within a stage of at most 1024 samples, in sample order, and the stages in fp64.  A non-finite
+ * point gives NaN.  n_samples = 0 gives zeros, n_points = 0 only counts; nothing is read out of bounds.
+ * Two launches: grid (tiles of 1024 points, `splits` contiguous sample ranges, planes) x 256 threads, a thread owns four
+ * points in registers and every lane reads a stage's samples from LDS as broadcasts; the second launch adds the ranges'
+ * fp64 partial sums in ascending order.  splits: 0 = cgv_kde_splits(n_planes, n_samples, n_points), a function of the
+ * three sizes alone, else 1 .. cgv_kde_max_splits().  No floating-point atomics: the same bits on every call.
+ * workspace: cgv_kde_workspace_bytes(n_planes, n_points, splits actually used) bytes, 8-byte aligned, contents need not
+ * survive.  Limits: cgv_kde_max_planes / _samples / _points(), n_planes * n_points <= 2^30; beyond a limit the call fails
+ * (CGV_E_BADARG) before any launch.  Bound: see DESIGN.md (K22 row). */
+int cgv_kde_max_planes(void);
+int cgv_kde_max_samples(void);
+int cgv_kde_max_points(void);
+int cgv_kde_max_splits(void);
+int cgv_kde_splits(int n_planes, int n_samples, int n_points);
+size_t cgv_kde_workspace_bytes(int n_planes, int n_points, int splits);
+int cgv_kde_sums(const float* samples, const float* points, const float* period /*or NULL*/, int n_planes, int n_samples,
+                 int n_points, int d, int splits, double* sums, int32_t* n_skipped, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
