@@ -85,7 +85,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import contacts, coverage, density, distributions, flexibility, tica
 from . import evaluate as ev
+from .analyses import ANALYSES, BY_STEM
 from .train import build_model
 
 
@@ -178,7 +180,7 @@ def backmap(model, cg_xyz, mapping, n_samples: int, cg_cutoff: float, *, z=None,
     check_topology(mapping, z, bonds)
     if bonds is not None and z is None:
         raise ValueError("a bond list needs the atomic numbers z (the bond cutoffs are per element pair)")
-    dev = ev._device_of(model)
+    dev = ev.model_device(model)
     bead_id = torch.arange(N).float()[:, None]                 # column 0 as build_dataset writes it
     cg_nxyz = [torch.cat([bead_id, cg[t]], dim=1) for t in range(T)]
     atoms = torch.empty(n, 4)                                  # ensemble_batch reads its row count only
@@ -193,7 +195,7 @@ def backmap(model, cg_xyz, mapping, n_samples: int, cg_cutoff: float, *, z=None,
     was_training = model.training
     try:
         with torch.no_grad():
-            ev._settle(model)
+            ev.settle(model)
             for start in range(0, T, M):
                 B = min(M, T - start)
                 rows = cg_nxyz[start:start + B]
@@ -221,7 +223,7 @@ def backmap(model, cg_xyz, mapping, n_samples: int, cg_cutoff: float, *, z=None,
                     plans[B] = (plan, ev.BondList(bonds, plan) if bonds is not None else None)
                 plan, bond_list = plans[B]
                 raw = ev.ensemble_check(gen, K, plan, bond_list)
-                gen_h, counts_h, sums_h = ev._read_back([gen, raw.counts, raw.pair_sums])
+                gen_h, counts_h, sums_h = ev.read_back([gen, raw.counts, raw.pair_sums])
                 out["xyz"][start:start + B] = gen_h.reshape(B, K, n, 3)
                 for f in range(B):
                     chk = ev.assemble_ensemble_check(counts_h[f], sums_h[f], n, int(plan.n_heavy[f]))
@@ -275,7 +277,7 @@ def backmap_valid(model, cg_xyz, mapping, n_samples: int, cg_cutoff: float, *, z
 def _check_only(model, xyz, cg, z, bonds, frames_per_launch, radii, scale) -> dict:
     """K14 over finished ensembles ``xyz [T,K,n,3]``: the entries of ``backmap``'s result."""
     T, K, n = xyz.shape[:3]
-    dev, M = ev._device_of(model), max(int(frames_per_launch), 1)
+    dev, M = ev.model_device(model), max(int(frames_per_launch), 1)
     out = {"xyz": xyz, "cg_xyz": cg.copy(), "pair_rmsd_all": np.empty((T, K, K)), "diversity_all": np.empty(T),
            "pair_rmsd_heavy": np.empty((T, K, K)), "diversity_heavy": np.empty(T), "counts": np.empty((T, K, 4), np.int32),
            "valid_all": np.empty((T, K), bool), "valid_heavy": np.empty((T, K), bool)}
@@ -287,7 +289,7 @@ def _check_only(model, xyz, cg, z, bonds, frames_per_launch, radii, scale) -> di
             plans[B] = (plan, ev.BondList(bonds, plan))
         plan, bond_list = plans[B]
         raw = ev.ensemble_check(torch.from_numpy(xyz[start:start + B].reshape(-1, 3)).to(dev), K, plan, bond_list)
-        counts_h, sums_h = ev._read_back([raw.counts, raw.pair_sums])
+        counts_h, sums_h = ev.read_back([raw.counts, raw.pair_sums])
         for f in range(B):
             chk, t = ev.assemble_ensemble_check(counts_h[f], sums_h[f], n, int(plan.n_heavy[f])), start + f
             out["pair_rmsd_all"][t], out["diversity_all"][t] = chk.pair_rmsd_all, chk.diversity_all
@@ -357,22 +359,25 @@ def build_parser() -> argparse.ArgumentParser:
 
 CONTACT_DEFAULTS = {"contact_stats": False, "contact_cutoff": 4.5, "contact_atoms": "heavy", "contact_exclude": 3,
                     "contact_groups": "none"}
+FLEX_DEFAULTS = {"flex_stats": False, "flex_atoms": "heavy", "flex_groups": "none", "flex_aligned": None}
+KDE_DEFAULTS = {"kde_stats": False, "kde_plane": "torsion", "kde_grid": 100, "kde_bw": "scott"}
+
+
+def _option_group(args, defaults: dict) -> dict:
+    """A switch and its options as parsed, with their defaults where they were not given (they are absent then)."""
+    return {k: getattr(args, k, v) for k, v in defaults.items()}
 
 
 def contact_args(args) -> dict:
-    """The ``--contact_stats`` switches of parsed arguments, with their defaults where they were not given."""
-    return {k: getattr(args, k, v) for k, v in CONTACT_DEFAULTS.items()}
-
-
-FLEX_DEFAULTS = {"flex_stats": False, "flex_atoms": "heavy", "flex_groups": "none", "flex_aligned": None}
+    return _option_group(args, CONTACT_DEFAULTS)
 
 
 def flex_args(args) -> dict:
-    """The ``--flex_stats`` switches of parsed arguments, with their defaults where they were not given."""
-    return {k: getattr(args, k, v) for k, v in FLEX_DEFAULTS.items()}
+    return _option_group(args, FLEX_DEFAULTS)
 
 
-KDE_DEFAULTS = {"kde_stats": False, "kde_plane": "torsion", "kde_grid": 100, "kde_bw": "scott"}
+def kde_args(args) -> dict:
+    return _option_group(args, KDE_DEFAULTS)
 
 
 def kde_bandwidth(text: str):
@@ -386,11 +391,6 @@ def kde_bandwidth(text: str):
     if not (value > 0 and np.isfinite(value)):
         raise argparse.ArgumentTypeError("scott, silverman or a positive number")
     return value
-
-
-def kde_args(args) -> dict:
-    """The ``--kde_stats`` switches of parsed arguments, with their defaults where they were not given."""
-    return {k: getattr(args, k, v) for k, v in KDE_DEFAULTS.items()}
 
 
 def _npz(path: str, need) -> dict:
@@ -409,8 +409,8 @@ def read_inputs(args, params, device=None) -> dict:
     mapping = np.asarray(params["mapping"], dtype=np.int64)
     n, N = mapping.shape[0], int(mapping.max()) + 1
     z = bonds = ref_xyz = None
-    dist_stats, tica_stats = getattr(args, "dist_stats", False), getattr(args, "tica_stats", False)
-    cov_stats = getattr(args, "cov_stats", False)
+    on = [f"--{a.stem}_stats" for a in ANALYSES if getattr(args, a.stem + "_stats", False)]
+    tica_stats, cov_stats = "--tica_stats" in on, "--cov_stats" in on
     contact, flex = contact_args(args), flex_args(args)
     if not flex["flex_stats"] and any(getattr(args, k, None) is not None for k in ("flex_atoms", "flex_groups", "flex_aligned")):
         raise SystemExit("-flex_atoms / -flex_groups / -flex_aligned are options of --flex_stats")
@@ -418,9 +418,9 @@ def read_inputs(args, params, device=None) -> dict:
     if not kde["kde_stats"] and any(getattr(args, k, None) is not None for k in ("kde_plane", "kde_grid", "kde_bw")):
         raise SystemExit("-kde_plane / -kde_grid / -kde_bw are options of --kde_stats")
     kde_tica = kde["kde_stats"] and kde["kde_plane"] == "tica"
-    need_ref, starts = dist_stats or tica_stats or cov_stats or contact["contact_stats"] or flex["flex_stats"] or kde["kde_stats"], None
+    need_ref, starts = bool(on), None
     if getattr(args, "ref", None) and not need_ref:
-        raise SystemExit("-ref is the reference of --dist_stats / --tica_stats / --cov_stats / --contact_stats / --flex_stats / --kde_stats")
+        raise SystemExit("-ref is the reference of " + " / ".join(f"--{a.stem}_stats" for a in ANALYSES))
     if args.cg:
         cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
@@ -448,8 +448,7 @@ def read_inputs(args, params, device=None) -> dict:
     if args.require_valid and bonds is None:
         raise SystemExit("--require_valid needs a topology (-top, or the z / bonds of -traj)")
     if need_ref:
-        switch = ("--dist_stats" if dist_stats else "--tica_stats" if tica_stats else "--cov_stats" if cov_stats else
-                  "--contact_stats" if contact["contact_stats"] else "--flex_stats" if flex["flex_stats"] else "--kde_stats")
+        switch = on[0]                                         # the first one asked for, in the table's order
         if bonds is None:
             raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
@@ -462,7 +461,6 @@ def read_inputs(args, params, device=None) -> dict:
         if ref_xyz is None or ref_xyz.shape[0] < 2:
             raise SystemExit(f"{switch} needs reference frames: -ref file.npz (or -traj as the source), at least two")
         if tica_stats or kde_tica:
-            from . import tica
             if args.tica_lag < 1 or ref_xyz.shape[0] < args.tica_lag + 2:
                 raise SystemExit(f"{'--tica_stats' if tica_stats else '--kde_stats -kde_plane tica'} needs 1 <= -tica_lag and at least lag + 2 reference frames: {ref_xyz.shape[0]} "
                                  f"frames, lag {args.tica_lag}")
@@ -473,13 +471,11 @@ def read_inputs(args, params, device=None) -> dict:
             except ValueError as err:
                 raise SystemExit(f"{'--tica_stats' if tica_stats else '--kde_stats'}: {err}")
         if cov_stats:
-            from . import coverage
             if not args.cov_thresholds or min(args.cov_thresholds) <= 0:
                 raise SystemExit("--cov_stats: -cov_thresholds must be positive RMSDs in Angstrom")
             if coverage.select_atoms(z, args.cov_atoms).shape[0] == 0:
                 raise SystemExit(f"--cov_stats: the topology has no {args.cov_atoms} atoms to superpose")
         if contact["contact_stats"]:
-            from . import contacts, coverage
             if not contact["contact_cutoff"] > 0 or contact["contact_exclude"] < 0:
                 raise SystemExit("--contact_stats: -contact_cutoff must be a positive distance in Angstrom, -contact_exclude >= 0")
             if coverage.select_atoms(z, contact["contact_atoms"]).shape[0] < 2:
@@ -490,7 +486,6 @@ def read_inputs(args, params, device=None) -> dict:
                 except ValueError as err:
                     raise SystemExit(f"--contact_stats: {err}")
         if flex["flex_stats"]:
-            from . import contacts, coverage
             if coverage.select_atoms(z, flex["flex_atoms"]).shape[0] < 3:
                 raise SystemExit(f"--flex_stats: the topology has fewer than three {flex['flex_atoms']} atoms: no rotation to fit")
             if flex["flex_groups"] == "residue":
@@ -499,7 +494,6 @@ def read_inputs(args, params, device=None) -> dict:
                 except ValueError as err:
                     raise SystemExit(f"--flex_stats: {err}")
         if kde["kde_stats"]:
-            from . import distributions
             if kde["kde_grid"] < 2:
                 raise SystemExit("--kde_stats: -kde_grid must be at least 2 nodes per axis")
             if ref_xyz.shape[0] < 4:
@@ -510,6 +504,13 @@ def read_inputs(args, params, device=None) -> dict:
         raise SystemExit("the run was trained with --cg_radius_graph (bead graph from the bonds): pass a topology")
     return {"cg_xyz": cg, "z": z, "bonds": bonds, "mapping": mapping, **({"ref_xyz": ref_xyz} if need_ref else {}),
             **({"ref_starts": starts} if tica_stats or kde_tica else {})}
+
+
+def _write_stats(out: str, stem: str, stats: dict) -> dict:
+    """The full statistics of an analysis go to ``<stem>_stats.json`` next to ``-out``, their short form to the summary line."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(out)), stem + "_stats.json"), "w") as f:
+        json.dump(stats, f)
+    return BY_STEM[stem].module.summary_of(stats)
 
 
 def run(args) -> dict:
@@ -554,45 +555,30 @@ def run(args) -> dict:
     T, K = res["xyz"].shape[:2]
     dist = {}
     if args.dist_stats:
-        from . import distributions
         stats = distributions.compare(inp["ref_xyz"], res["xyz"].reshape(T * K, -1, 3), z, bonds, device=device)
-        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "dist_stats.json"), "w") as f:
-            json.dump(stats, f)
-        dist = {"dist_stats": distributions.summary_of(stats)}
+        dist["dist_stats"] = _write_stats(args.out, "dist", stats)
     if args.tica_stats:
-        from . import tica
         stats = tica.compare(tica.split_segments(inp["ref_xyz"], inp["ref_starts"]), res["xyz"].reshape(T * K, -1, 3), z, bonds,
                              lag=args.tica_lag, n_bins2=args.tica_bins, device=device)
-        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "tica_stats.json"), "w") as f:
-            json.dump(stats, f)
-        dist["tica_stats"] = tica.summary_of(stats)
+        dist["tica_stats"] = _write_stats(args.out, "tica", stats)
     if args.cov_stats:
-        from . import coverage
         stats = coverage.compare(inp["ref_xyz"], res["xyz"].reshape(T * K, -1, 3), z, thresholds=args.cov_thresholds,
                                  atoms=args.cov_atoms, device=device)
-        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "cov_stats.json"), "w") as f:
-            json.dump(stats, f)
-        dist["cov_stats"] = coverage.summary_of(stats)
+        dist["cov_stats"] = _write_stats(args.out, "cov", stats)
     contact = contact_args(args)
     if contact["contact_stats"]:
-        from . import contacts
         stats = contacts.compare(inp["ref_xyz"], res["xyz"].reshape(T * K, -1, 3), z, bonds, atoms=contact["contact_atoms"],
                                  cutoff=contact["contact_cutoff"], exclude=contact["contact_exclude"],
                                  groups=None if contact["contact_groups"] == "none" else contact["contact_groups"],
                                  mapping=mapping, device=device)
-        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "contact_stats.json"), "w") as f:
-            json.dump(stats, f)
-        dist["contact_stats"] = contacts.summary_of(stats)
+        dist["contact_stats"] = _write_stats(args.out, "contact", stats)
     flex = flex_args(args)
     if flex["flex_stats"]:
-        from . import coverage, flexibility
         gen = res["xyz"].reshape(T * K, -1, 3)
         stats = flexibility.compare(inp["ref_xyz"], gen, z, bonds, atoms=flex["flex_atoms"],
                                     groups=None if flex["flex_groups"] == "none" else flex["flex_groups"], mapping=mapping,
                                     device=device)
-        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "flex_stats.json"), "w") as f:
-            json.dump(stats, f)
-        dist["flex_stats"] = flexibility.summary_of(stats)
+        dist["flex_stats"] = _write_stats(args.out, "flex", stats)
         if flex["flex_aligned"]:
             sel = coverage.select_atoms(z, flex["flex_atoms"])
             own = flexibility.mean_structure(gen, sel, device=device)
@@ -602,7 +588,6 @@ def run(args) -> dict:
                                 rmsf=own["rmsf"], atoms=sel.astype(np.int64))
     kde = kde_args(args)
     if kde["kde_stats"]:
-        from . import density, tica
         gen = res["xyz"].reshape(T * K, -1, 3)
         try:
             if kde["kde_plane"] == "torsion":
@@ -612,9 +597,7 @@ def run(args) -> dict:
                                              n_grid=kde["kde_grid"], bandwidth=kde["kde_bw"], device=device)
         except ValueError as err:
             raise SystemExit(f"--kde_stats: {err}")
-        with open(os.path.join(os.path.dirname(os.path.abspath(args.out)), "kde_stats.json"), "w") as f:
-            json.dump(stats, f)
-        dist["kde_stats"] = density.summary_of(stats)
+        dist["kde_stats"] = _write_stats(args.out, "kde", stats)
 
     def mean(key):
         if key not in res:

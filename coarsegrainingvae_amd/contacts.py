@@ -15,6 +15,8 @@ every count exactly.  Two groups are in contact in a structure iff ANY non-exclu
 be derived from the atom counts: the "any" is taken per structure).  The result is a ``[m, m]`` (or ``[G, G]``) table of
 integers -- no ``[S, m, m]`` tensor exists -- and four numbers per structure.  A structure with a non-finite selected
 coordinate is *bad*: it is counted nowhere, its ``n_contacts`` and ``n_native`` are ``-1`` and its ``rg2`` is NaN.
+
+The host pieces shared with the other analyses (``selection``, ``groups_of``, ``scalar_block``, ...) live in ``ensemble``.
 """
 from __future__ import annotations
 
@@ -23,17 +25,15 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib
-from .coverage import _structures, select_atoms
-from .distributions import _adjacency, _peptide_residues, js_divergence
+from . import _lib, ensemble
+from .ensemble import adjacency, check_sets, device_of, groups_of, read_back, scalar_block, select_atoms, structures
 
 MAX_GROUPS = 4096                      # include/cgvae_hip.h: the group kernel's grid
 WORKSPACE_BYTES = 1 << 28              # structures_per_launch is lowered until the packed copy of a launch fits this
 
 
 def limits() -> Dict[str, int]:
-    lib = _lib.load()
-    return {k: int(getattr(lib, "cgv_contact_max_" + k)()) for k in ("structures", "atoms")}
+    return ensemble.limits("contact")
 
 
 def cutoff2_of(cutoff: float) -> np.float32:
@@ -54,7 +54,7 @@ def excluded_pairs(bonds, n_atoms: int, sel, depth: int = 3) -> np.ndarray:
     sel = np.asarray(sel, dtype=np.int64).reshape(-1)
     if sel.shape[0] and (sel.min() < 0 or sel.max() >= n_atoms):
         raise ValueError(f"the selection names atom {int(sel.max() if sel.max() >= n_atoms else sel.min())}, the molecule has {n_atoms} atoms")
-    nbrs = _adjacency(int(n_atoms), bonds)
+    nbrs = adjacency(int(n_atoms), bonds)
     where = {}
     for k, a in enumerate(sel.tolist()):
         where.setdefault(a, []).append(k)
@@ -70,47 +70,6 @@ def excluded_pairs(bonds, n_atoms: int, sel, depth: int = 3) -> np.ndarray:
     return out
 
 
-def groups_of(z, bonds, mapping=None, kind: str = "bead") -> np.ndarray:
-    """A group label for every atom of the molecule, ``[n]`` int64.  ``"bead"``: the coarse-graining ``mapping``.
-    ``"residue"``: the residues of a peptide found from elements and connectivity (``distributions._peptide_residues``:
-    N - CA - C'), numbered in the order of their N; every other atom joins the residue whose backbone is the fewest bonds
-    away (a carbonyl O its C', a side chain its CA, a terminal cap the residue it is bonded to).  ``ValueError`` when
-    the molecule has no such backbone, or an atom is not connected to one."""
-    z = np.asarray(z).astype(np.int64).reshape(-1)
-    n = z.shape[0]
-    if kind == "bead":
-        if mapping is None:
-            raise ValueError("groups of kind 'bead' need the coarse-graining mapping")
-        m = np.asarray(mapping, dtype=np.int64).reshape(-1)
-        if m.shape[0] != n:
-            raise ValueError(f"the mapping lists {m.shape[0]} atoms, z has {n}")
-        return m
-    if kind != "residue":
-        raise ValueError("kind must be 'bead' or 'residue'")
-    nbrs = _adjacency(n, bonds)
-    _, residues = _peptide_residues(z, nbrs)
-    if not residues:
-        raise ValueError("groups of kind 'residue' need a peptide: no N - CA - C' backbone was found in the bond graph")
-    label = np.full(n, -1, dtype=np.int64)
-    r = 0
-    for triple in residues:                                   # in the order of N
-        if all(label[a] < 0 for a in triple):
-            label[list(triple)] = r
-            r += 1
-    frontier = [a for a in range(n) if label[a] >= 0]         # ascending: ties go to the atom met first
-    while frontier:
-        nxt = []
-        for a in frontier:
-            for b in nbrs[a]:
-                if label[b] < 0:
-                    label[b] = label[a]
-                    nxt.append(b)
-        frontier = nxt
-    if (label < 0).any():
-        raise ValueError(f"atom {int(np.flatnonzero(label < 0)[0])} is not connected to a peptide backbone: it belongs to no residue")
-    return label
-
-
 def _pack_bits(mask: np.ndarray) -> np.ndarray:
     """``[r, c]`` bool as the kernel's ``[r, ceil(c/32)]`` uint32: bit ``j & 31`` of word ``j >> 5``."""
     r, c = mask.shape
@@ -119,19 +78,6 @@ def _pack_bits(mask: np.ndarray) -> np.ndarray:
     padded[:, :c] = mask
     weights = (np.uint64(1) << np.arange(32, dtype=np.uint64))
     return np.ascontiguousarray((padded.reshape(r, words, 32).astype(np.uint64) * weights).sum(-1).astype(np.uint32))
-
-
-def _check_sel(sel, n_atoms: int) -> np.ndarray:
-    """The selection as the kernel takes it (int32 ``[m]``, in the caller's order; default: every atom); ``ValueError``
-    before any launch for an empty selection or an index outside ``[0, n_atoms)``."""
-    s = np.arange(n_atoms, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
-    if s.shape[0] == 0:
-        raise ValueError("the selection is empty (m = 0): no atoms to count contacts of")
-    if s.min() < 0 or s.max() >= n_atoms:
-        raise ValueError(f"the selection names atom {int(s.max() if s.max() >= n_atoms else s.min())}, a structure has {n_atoms} atoms")
-    if np.unique(s).shape[0] != s.shape[0]:
-        raise ValueError("the selection names an atom twice")
-    return np.ascontiguousarray(s.astype(np.int32))
 
 
 def _square(mask, size: int, what: str) -> np.ndarray:
@@ -161,14 +107,13 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
 
     The structures go through in launches of ``structures_per_launch``; the table is summed on the device in int64;
     ONE read-back.  Limits (``limits()``, total structures < 2^31, at most 4096 groups) are refused before any launch."""
-    from .evaluate import _read_back
-    x = _structures(xyz)
+    x = structures(xyz)
     S, n = int(x.shape[0]), int(x.shape[1])
     lim = limits()
     if S >= 2 ** 31:
         raise ValueError("the counts are int32: fewer than 2^31 structures")
     c2 = cutoff2_of(cutoff)
-    table = _check_sel(sel, n)
+    table = ensemble.selection(sel, n, purpose="count contacts of")
     m = int(table.shape[0])
     if m > lim["atoms"]:
         raise ValueError(f"the selection lists {m} atoms (the kernel holds {lim['atoms']})")
@@ -186,7 +131,7 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
         gstart = np.concatenate([[0], np.cumsum(np.bincount(dense, minlength=ids.shape[0]))]).astype(np.int32)
     P = m if groups is None else int(ids.shape[0])
     nat = None if native is None else _square(native, P, "native")
-    dev = x.device if x.is_cuda else torch.device(device)
+    dev = device_of(x, device)
     M = max(1, min(int(structures_per_launch), lim["structures"], max(64, WORKSPACE_BYTES // (16 * m))))
     total = torch.zeros(P, P, dtype=torch.int64, device=dev)
     part = torch.zeros(P, P, dtype=torch.int32, device=dev)
@@ -214,7 +159,7 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
                 _lib.call("cgv_contact_group_counts", _lib.ptr(chunk), _lib.ptr(d_sel), _lib.ptr(d_gs), _lib.ptr(d_excl),
                           _lib.ptr(d_nat), k, n, m, P, float(c2), _lib.ptr(part), *out, *tail, tag="contact_group_counts")
             total += part
-    counts, n_contacts, n_native, rg2, bad = _read_back([total] + [per[k] for k in ("n_contacts", "n_native", "rg2", "bad")])
+    counts, n_contacts, n_native, rg2, bad = read_back([total] + [per[k] for k in ("n_contacts", "n_native", "rg2", "bad")])
     res = {"counts": counts, "n_good": int(S - int(bad.sum())), "n_contacts": n_contacts.astype(np.int64),
            "n_native": n_native.astype(np.int64), "rg2": rg2, "bad": bad.astype(bool)}
     if groups is not None:
@@ -250,30 +195,6 @@ def _map_dev(p, q, upper):
     return float(np.sqrt(np.mean(d * d))), float(np.abs(d).max())
 
 
-def _hist(values: np.ndarray, lo: float, hi: float, n_bins: int) -> dict:
-    """``n_bins`` equal bins on ``[lo, hi]`` (the upper edge belongs to the last bin); what falls outside is counted in
-    ``under`` / ``over`` and left out, as ``distributions`` does."""
-    v = np.asarray(values, dtype=np.float64)
-    inside = v[(v >= lo) & (v <= hi)]
-    counts = np.histogram(inside, bins=int(n_bins), range=(lo, hi))[0] if hi > lo else np.zeros(int(n_bins), dtype=np.int64)
-    return {"counts": counts.astype(np.int64).tolist(), "under": int((v < lo).sum()), "over": int((v > hi).sum())}
-
-
-def _moments(v: np.ndarray):
-    return (float(v.mean()), float(v.std())) if v.size else (None, None)
-
-
-def _scalar_block(ref_e, ref_o, gen, lo, hi, n_bins) -> dict:
-    """Histograms, JSD with its even / odd floor, and the moments of one per-structure quantity."""
-    ref = np.concatenate([ref_e, ref_o])
-    he, ho, hg = _hist(ref_e, lo, hi, n_bins), _hist(ref_o, lo, hi, n_bins), _hist(gen, lo, hi, n_bins)
-    hr = {"counts": (np.asarray(he["counts"]) + np.asarray(ho["counts"])).tolist(), "under": he["under"] + ho["under"],
-          "over": he["over"] + ho["over"]}
-    (mr, sr), (mg, sg) = _moments(ref), _moments(gen)
-    return {"range": [float(lo), float(hi)], "hist_ref": hr, "hist_gen": hg, "jsd": js_divergence(hr["counts"], hg["counts"]),
-            "floor": js_divergence(he["counts"], ho["counts"]), "mean_ref": mr, "std_ref": sr, "mean_gen": mg, "std_gen": sg}
-
-
 def compare_from_counts(even: dict, odd: dict, gen: dict, allowed, native, labels=None, n_bins: int = 20,
                         params: Optional[dict] = None) -> dict:
     """The statistics of ``compare`` from three results of ``contact_counts`` -- the even reference frames, the odd ones
@@ -307,10 +228,10 @@ def compare_from_counts(even: dict, odd: dict, gen: dict, allowed, native, label
     if rg_ref.size and rg[2].size:
         lo, hi = float(rg_ref.min()), float(rg_ref.max())
         pad = 0.1 * (hi - lo) if hi > lo else 0.05 * max(abs(hi), 1.0)       # the reference's range, 20 % wider
-        rg_block = _scalar_block(rg[0], rg[1], rg[2], lo - pad, hi + pad, n_bins)
+        rg_block = scalar_block(rg[0], rg[1], rg[2], lo - pad, hi + pad, n_bins)
         if n_native > 0:
             q = [good(r, "n_native").astype(np.float64) / n_native for r in (even, odd, gen)]
-            q_block = _scalar_block(q[0], q[1], q[2], 0.0, 1.0, n_bins)
+            q_block = scalar_block(q[0], q[1], q[2], 0.0, 1.0, n_bins)
     n_of = lambda *rs: int(sum(np.asarray(r["bad"]).shape[0] for r in rs))
     n_bad = lambda *rs: int(sum(np.asarray(r["bad"], dtype=bool).sum() for r in rs))
     return {"n_ref": n_of(even, odd), "n_gen": n_of(gen), "n_bad_ref": n_bad(even, odd), "n_bad_gen": n_bad(gen),
@@ -346,14 +267,7 @@ def compare(ref_xyz, gen_xyz, z, bonds, atoms="heavy", cutoff: float = 4.5, excl
                   std_gen} of Q = n_native(s) / n_native on [0, 1] and of Rg (Angstrom) on the reference's range widened
                   by 20 %; ``None`` where a set has no good structure, ``q`` also when no pair is native
     """
-    ref, gen = _structures(ref_xyz), _structures(gen_xyz)
-    z = np.asarray(z).astype(np.int64).reshape(-1)
-    if int(ref.shape[0]) < 2:
-        raise ValueError("at least two reference frames are needed (the floor compares the even with the odd ones)")
-    if z.shape[0] != int(ref.shape[1]) or int(gen.shape[1]) != int(ref.shape[1]):
-        raise ValueError(f"z lists {z.shape[0]} atoms, the frames have {int(ref.shape[1])} and {int(gen.shape[1])}")
-    if groups not in (None, "bead", "residue"):
-        raise ValueError("groups must be None, 'bead' or 'residue'")
+    ref, gen, z = check_sets(ref_xyz, gen_xyz, z, groups=groups)
     sel = select_atoms(z, atoms)
     excl = excluded_pairs(bonds, z.shape[0], sel, exclude)
     glab = None if groups is None else groups_of(z, bonds, mapping, groups)[sel]

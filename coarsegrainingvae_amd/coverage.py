@@ -13,6 +13,8 @@ proper rotations only, a mirror image is not a superposition.  The nine cross-co
 fp64 GEMM on the matrix cores, the rotation solve and the nearest-neighbour reductions are the kernel's epilogue: no
 ``[Sa, Sb]`` tensor exists unless ``rmsd_matrix`` asks for it.  A structure with a non-finite selected coordinate is
 *bad*: NaN in the dense matrix, never a nearest neighbour, its own minimum ``+inf`` with index ``-1``.
+
+The host pieces shared with the other analyses (``structures``, ``selection``, ``read_back``, ...) live in ``ensemble``.
 """
 from __future__ import annotations
 
@@ -21,43 +23,22 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ensemble
+from .ensemble import check_sets, device_of, read_back, select_atoms, structures
 
 MAX_DENSE_PAIRS = 1 << 24
 
 
 def limits() -> Dict[str, int]:
-    lib = _lib.load()
-    return {k: int(getattr(lib, "cgv_superpose_max_" + k)()) for k in ("structures", "atoms")}
-
-
-def _structures(x) -> torch.Tensor:
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
-    if t.dim() != 3 or t.shape[2] != 3:
-        raise ValueError(f"structures must be [S, n, 3], got {tuple(t.shape)}")
-    return t
-
-
-def _check_sel(sel, n_atoms: int) -> np.ndarray:
-    """The selection as the kernel takes it (int32 ``[m]``, in the caller's order; default: every atom); ``ValueError``
-    before any launch for an empty selection or an index outside ``[0, n_atoms)``."""
-    if n_atoms > limits()["atoms"]:
-        raise ValueError(f"{n_atoms} atoms per structure (the kernel holds {limits()['atoms']})")
-    s = np.arange(n_atoms, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
-    if s.shape[0] == 0:
-        raise ValueError("the selection is empty (m = 0): no atoms to superpose")
-    if s.shape[0] > n_atoms:
-        raise ValueError(f"the selection lists {s.shape[0]} atoms, a structure has {n_atoms}")
-    if s.min() < 0 or s.max() >= n_atoms:
-        raise ValueError(f"the selection names atom {int(s.max() if s.max() >= n_atoms else s.min())}, a structure has {n_atoms} atoms")
-    return np.ascontiguousarray(s.astype(np.int32))
+    return ensemble.limits("superpose")
 
 
 def _pair_of_sets(a, b, sel):
-    a, b = _structures(a), _structures(b)
+    """Both sets as tensors and the selection as the kernel takes it (it may name an atom more than once)."""
+    a, b = structures(a), structures(b)
     if int(a.shape[1]) != int(b.shape[1]):
         raise ValueError(f"the two sets have different atom counts (mismatched n): {int(a.shape[1])} and {int(b.shape[1])}")
-    return a, b, _check_sel(sel, int(a.shape[1]))
+    return a, b, ensemble.selection(sel, int(a.shape[1]), purpose="superpose", unique=False, max_atoms=limits()["atoms"])
 
 
 def new_state(sa: int, sb: int, device) -> Dict[str, torch.Tensor]:
@@ -88,7 +69,7 @@ def superpose_launch(a: torch.Tensor, b: torch.Tensor, sel: torch.Tensor, row_mi
         raise ValueError("dense must be [sa, sb] float64")
     need = int(_lib.load().cgv_superpose_workspace_bytes(sa, sb))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=a.device)
+        workspace = ensemble.workspace(need, a.device)
     _lib.call("cgv_superpose", _lib.ptr(a), _lib.ptr(b), _lib.ptr(sel), sa, sb, n, m, int(off_a), int(off_b), int(bool(same)),
               _lib.ptr(row_min), _lib.ptr(row_arg), _lib.ptr(col_min), _lib.ptr(col_arg), _lib.ptr(dense), _lib.ptr(workspace),
               workspace.numel() * workspace.element_size(), _lib.stream_ptr(), tag="superpose")
@@ -97,7 +78,6 @@ def superpose_launch(a: torch.Tensor, b: torch.Tensor, sel: torch.Tensor, row_mi
 def rmsd_matrix(a, b, sel=None, device="cuda") -> np.ndarray:
     """The dense superposed RMSD ``[Sa, Sb]`` (host, fp64; NaN for a pair with a bad structure) of two small sets over the
     atoms ``sel`` (default: all).  More than 2^24 pairs are refused: use ``nearest``."""
-    from .evaluate import _read_back
     a, b, table = _pair_of_sets(a, b, sel)
     sa, sb = int(a.shape[0]), int(b.shape[0])
     if sa * sb > MAX_DENSE_PAIRS:
@@ -107,11 +87,11 @@ def rmsd_matrix(a, b, sel=None, device="cuda") -> np.ndarray:
         raise ValueError(f"a launch holds {lim} structures per set")
     if sa == 0 or sb == 0:
         return np.zeros((sa, sb), dtype=np.float64)
-    dev = a.device if a.is_cuda else torch.device(device)
+    dev = device_of(a, device)
     xa, xb = a.detach().to(dev, torch.float32).contiguous(), b.detach().to(dev, torch.float32).contiguous()
     dense = torch.empty(sa, sb, dtype=torch.float64, device=dev)
     superpose_launch(xa, xb, torch.from_numpy(table).to(dev), **new_state(sa, sb, dev), dense=dense)
-    return np.sqrt(_read_back([dense])[0])
+    return np.sqrt(read_back([dense])[0])
 
 
 def nearest(a, b, sel=None, exclude_self: bool = False, structures_per_launch: int = 4096, device="cuda"):
@@ -121,26 +101,25 @@ def nearest(a, b, sel=None, exclude_self: bool = False, structures_per_launch: i
     one, or every partner bad) has ``(+inf, -1)``.  ``exclude_self``: the pairs ``i == j`` are skipped (``b`` is the same
     set as ``a``).  Both sets are cut into chunks of ``structures_per_launch``, one launch per pair of chunks, the running
     minima stay on the device (the result does not depend on the chunk size, bit for bit); ONE read-back."""
-    from .evaluate import _read_back
     a, b, table = _pair_of_sets(a, b, sel)
     sa, sb = int(a.shape[0]), int(b.shape[0])
     M = min(max(int(structures_per_launch), 1), limits()["structures"])
     if max(sa, sb) > 2 ** 31 - 1:
         raise ValueError("structure indices are int32")
-    dev = a.device if a.is_cuda else torch.device(device)
+    dev = device_of(a, device)
     state = new_state(sa, sb, dev)
     if sa and sb:
         stab = torch.from_numpy(table).to(dev)
         xa = a.detach().to(dev, torch.float32).contiguous()
         xb = xa if b is a else b.detach().to(dev, torch.float32).contiguous()
         need = int(_lib.load().cgv_superpose_workspace_bytes(min(M, sa), min(M, sb)))
-        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=dev)
+        workspace = ensemble.workspace(need, dev)
         for oa in range(0, sa, M):
             for ob in range(0, sb, M):
                 ea, eb = min(oa + M, sa), min(ob + M, sb)
                 superpose_launch(xa[oa:ea], xb[ob:eb], stab, state["row_min"][oa:ea], state["row_arg"][oa:ea],
                                  state["col_min"][ob:eb], state["col_arg"][ob:eb], oa, ob, exclude_self, workspace=workspace)
-    row_min, row_arg, col_min, col_arg = _read_back([state[k] for k in ("row_min", "row_arg", "col_min", "col_arg")])
+    row_min, row_arg, col_min, col_arg = read_back([state[k] for k in ("row_min", "row_arg", "col_min", "col_arg")])
     return np.sqrt(row_min), row_arg.astype(np.int64), np.sqrt(col_min), col_arg.astype(np.int64)
 
 
@@ -174,16 +153,6 @@ METRIC_KEYS = ("thresholds", "cov_r", "mat_r_mean", "mat_r_median", "cov_p", "ma
                "unmatched_p")
 
 
-def select_atoms(z, atoms="heavy") -> np.ndarray:
-    """``"heavy"``: every atom that is not hydrogen; ``"all"``; or an index array, taken as it is."""
-    z = np.asarray(z).astype(np.int64).reshape(-1)
-    if isinstance(atoms, str):
-        if atoms not in ("heavy", "all"):
-            raise ValueError("atoms must be 'heavy', 'all' or an index array")
-        return np.flatnonzero(z != 1) if atoms == "heavy" else np.arange(z.shape[0])
-    return np.asarray(atoms, dtype=np.int64).reshape(-1)
-
-
 def compare(ref_xyz, gen_xyz, z, thresholds=(0.5, 1.0, 2.0), atoms="heavy", structures_per_launch: int = 4096,
             device="cuda") -> dict:
     """Generated structures ``gen_xyz [Sg,n,3]`` against reference frames ``ref_xyz [Sr,n,3]`` (at least two) by
@@ -197,12 +166,9 @@ def compare(ref_xyz, gen_xyz, z, thresholds=(0.5, 1.0, 2.0), atoms="heavy", stru
                    on COV, not the value a perfect generator reaches.
       nearest_ref  [n_ref] how many generated structures have reference frame r as their nearest (sums to ``n_gen``
                    less ``unmatched_p``): frames no sample chose, and frames that attract most samples, are visible"""
-    ref, gen = _structures(ref_xyz), _structures(gen_xyz)
+    ref, gen = structures(ref_xyz), structures(gen_xyz)
     sel = select_atoms(z, atoms)
-    if int(ref.shape[0]) < 2:
-        raise ValueError("at least two reference frames are needed (the floor compares the even with the odd ones)")
-    if np.asarray(z).reshape(-1).shape[0] != int(ref.shape[1]):
-        raise ValueError(f"z lists {np.asarray(z).reshape(-1).shape[0]} atoms, a reference frame has {int(ref.shape[1])}")
+    check_sets(ref, gen, z, gen_width=False)                  # nearest() refuses a generated set of another width
     kw = dict(structures_per_launch=structures_per_launch, device=device)
     row_min, _, col_min, col_arg = nearest(ref, gen, sel, **kw)
     even_min, _, odd_min, _ = nearest(ref[0::2], ref[1::2], sel, **kw)

@@ -12,6 +12,8 @@ with the noise floor between the even and the odd reference frames.  No figure i
 The host centres, whitens and scales the coordinates in fp64 (``_Frame``): with ``H = L L^T`` and ``c = sqrt(log2(e) / 2)``,
 ``u = c L^-1 (x - mean)`` turns ``exp(-(x - y)^T H^-1 (x - y) / 2)`` into ``exp2(-|u_x - u_y|^2)``, which is all the kernel
 computes.  Centring is what keeps the fp32 coordinates small: data at 1000 +- 1 loses nothing.
+
+The host pieces shared with the other analyses (``js_divergence``, ``read_back``, ``workspace``) live in ``ensemble``.
 """
 from __future__ import annotations
 
@@ -21,8 +23,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, options
-from .distributions import js_divergence
+from . import _lib, ensemble, options, tica
+from .distributions import TORSION, InternalCoords, feature_values, peptide_backbone_torsions
+from .ensemble import js_divergence, read_back
 
 WORKSPACE_BYTES = 1 << 26              # the points of a launch are cut until the ranges' partial sums fit this
 SCALE = math.sqrt(0.5 * math.log2(math.e))
@@ -30,8 +33,7 @@ MAX_WIDTH_FRACTION = 1.0 / 12.0        # of the period: beyond the nearest image
 
 
 def limits() -> Dict[str, int]:
-    lib = _lib.load()
-    return {k: int(getattr(lib, "cgv_kde_max_" + k)()) for k in ("planes", "samples", "points", "splits")}
+    return ensemble.limits("kde", ("planes", "samples", "points", "splits"))
 
 
 # ----------------------------------------------------------------------------- the launch
@@ -59,7 +61,7 @@ def kde_sums(samples: torch.Tensor, points: torch.Tensor, period: Optional[torch
     used = splits if splits else int(lib.cgv_kde_splits(P, N, M))
     need = int(lib.cgv_kde_workspace_bytes(P, M, used))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(max((need + 7) // 8, 1), dtype=torch.float64, device=samples.device)
+        workspace = ensemble.workspace(max(need, 8), samples.device)
     sums = torch.empty((P, M), dtype=torch.float64, device=samples.device)
     skipped = torch.zeros(P, dtype=torch.int32, device=samples.device)
     if P:
@@ -233,7 +235,6 @@ def _evaluate_many(kdes: Sequence[Kde], points_list: Sequence) -> List[np.ndarra
     """The densities of ``kdes[p]`` at ``points_list[p]``.  Planes of one ``d`` share launches: samples are padded to the
     longest plane with NaN rows (the kernel skips them) and points with zeros, the points are cut into chunks whose
     partial sums fit ``WORKSPACE_BYTES``; ONE read-back."""
-    from .evaluate import _read_back
     if len(kdes) != len(points_list):
         raise ValueError("one set of points per plane")
     pts = [_array(q, "points", k.d) for k, q in zip(kdes, points_list)]
@@ -267,7 +268,7 @@ def _evaluate_many(kdes: Sequence[Kde], points_list: Sequence) -> List[np.ndarra
                 parts.append(kde_sums(s_t, chunk, w_t)[0])
             sums = torch.cat(parts, dim=1) if parts else torch.zeros((P, 0), dtype=torch.float64, device=dev)
             pending.append((group, sums))
-    back = _read_back([s for _, s in pending]) if pending else []
+    back = read_back([s for _, s in pending]) if pending else []
     for (group, _), sums in zip(pending, back):
         for row, i in enumerate(group):
             out[i] = sums[row, :pts[i].shape[0]] / kdes[i].norm
@@ -384,7 +385,6 @@ def _means(planes: Sequence[dict]) -> dict:
 def torsion_pairs(z, bonds):
     """``(coords, rows)``: the backbone torsions of a peptide as a feature table of their own, and the (phi row, psi row)
     of every residue that has both (``distributions.peptide_backbone_torsions``)."""
-    from .distributions import TORSION, InternalCoords, peptide_backbone_torsions
     z = np.asarray(z).astype(np.int64).reshape(-1)
     phi, psi, pairs = peptide_backbone_torsions(z, bonds)
     if not pairs:
@@ -403,7 +403,6 @@ def compare_torsions(ref_xyz, gen_xyz, z, bonds, n_grid: int = 100, bandwidth="s
     ``n_ref``, ``n_gen``, ``n_bad_ref``, ``n_bad_gen``, ``pairs`` (a ``compare_planes`` dict per residue, with the ``phi``
     and ``psi`` atoms) and ``mean`` (the means of jsd, floor, fe_rmse, fe_floor, loglik_gen, loglik_floor over the
     pairs).  ``ValueError``: no peptide backbone."""
-    from .distributions import feature_values
     coords, rows = torsion_pairs(z, bonds)
     kw = dict(structures_per_launch=structures_per_launch, device=device)
     tr, tg = feature_values(ref_xyz, coords, **kw), feature_values(gen_xyz, coords, **kw)
@@ -425,8 +424,7 @@ def compare_tica(ref_trajs, gen_xyz, z, bonds, lag: int = 100, n_grid: int = 100
     plane of the reference's two slowest independent components (``tica.fit`` / ``tica.project`` as ``tica.compare``
     uses them), then ``compare_planes``.  The result carries ``plane`` (``"tica"``), ``lag``, ``eigenvalues`` and, like
     ``compare_torsions``, a one-entry ``pairs`` and ``mean``."""
-    from . import tica
-    segs = [tica._frames(x) for x in ref_trajs]
+    segs = [tica.frames(x) for x in ref_trajs]
     z = np.asarray(z).astype(np.int64).reshape(-1)
     if sel is None:
         sel = tica.backbone_atoms(z, bonds)
@@ -434,7 +432,7 @@ def compare_tica(ref_trajs, gen_xyz, z, bonds, lag: int = 100, n_grid: int = 100
             raise ValueError("the molecule has no peptide backbone: pass the atoms to use as sel")
     model = tica.fit(segs, tica.distance_pairs(sel, excluded_neighbors), lag, dim=2, device=device)
     ref = torch.cat([s.detach().cpu() for s in segs]) if len(segs) > 1 else segs[0]
-    ics_ref, ics_gen = tica.project(ref, model, device=device), tica.project(tica._frames(gen_xyz), model, device=device)
+    ics_ref, ics_gen = tica.project(ref, model, device=device), tica.project(tica.frames(gen_xyz), model, device=device)
     if ics_ref.shape[1] < 2:
         raise ValueError("the TICA model has one component: there is no (IC1, IC2) plane")
     good = np.isfinite(ics_gen[:, :2]).all(1)

@@ -8,6 +8,9 @@ features and of the (phi, psi) pairs come from ONE launch per chunk of structure
 stored.  The counts are exact integers; everything after them (``js_divergence``, ``compare``) is fp64 on the host.
 
 Row layout of a feature's histogram: ``[under, n_bins bins, over, invalid]`` (``UNDER``, ``OVER``, ``INVALID`` below).
+
+The host pieces shared with the other analyses (``adjacency``, ``peptide_residues``, ``js_divergence``, ``read_back``)
+live in ``ensemble``.
 """
 from __future__ import annotations
 
@@ -17,7 +20,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ensemble
+from .ensemble import adjacency, device_of, js_divergence, peptide_residues, read_back
 
 BOND, ANGLE, TORSION = 2, 3, 4
 KIND_NAMES = {BOND: "bond", ANGLE: "angle", TORSION: "torsion"}
@@ -57,18 +61,6 @@ class InternalCoords:
         return InternalCoords(self.feat, self.kind, np.asarray(pairs, dtype=np.int32).reshape(-1, 2), self.n_atoms)
 
 
-def _adjacency(n: int, bonds) -> List[List[int]]:
-    b = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)
-    if b.shape[0] and (b.min() < 0 or b.max() >= n):
-        raise ValueError(f"bonds name atom {int(b.max())}, z has {n} atoms")
-    nbrs = [set() for _ in range(n)]
-    for i, j in b.tolist():
-        if i != j:
-            nbrs[i].add(j)
-            nbrs[j].add(i)
-    return [sorted(s) for s in nbrs]
-
-
 def internal_coords(z, bonds, which: str = "all") -> InternalCoords:
     """Every bond, angle and proper torsion of the bond graph, each once: bonds ``(i, j)`` with ``i < j``; angles
     ``i-j-k`` with ``i < k`` around every atom ``j``; torsions ``i-j-k-l`` for every bond ``j-k`` (``j < k``), every
@@ -78,7 +70,7 @@ def internal_coords(z, bonds, which: str = "all") -> InternalCoords:
         raise ValueError("which must be 'all' or 'heavy'")
     z = np.asarray(z).astype(np.int64).reshape(-1)
     n = z.shape[0]
-    nbrs = _adjacency(n, bonds)
+    nbrs = adjacency(n, bonds)
     rows = []
     for i in range(n):
         rows += [(BOND, i, j, 0, 0) for j in nbrs[i] if i < j]
@@ -102,8 +94,8 @@ def peptide_backbone_torsions(z, bonds):
     ``psi`` are lists of atom 4-tuples, ``pairs`` lists ``(index into phi, index into psi)`` of the residues that have
     both.  Nothing matches (a hydrocarbon): three empty lists."""
     z = np.asarray(z).astype(np.int64).reshape(-1)
-    nbrs = _adjacency(z.shape[0], bonds)
-    is_amide, residues = _peptide_residues(z, nbrs)
+    nbrs = adjacency(z.shape[0], bonds)
+    is_amide, residues = peptide_residues(z, nbrs)
     phi, psi, pairs = [], [], []
     for N, CA, C in residues:
         mine_phi = [(Cp, N, CA, C) for Cp in nbrs[N] if is_amide[Cp] and Cp not in (C, CA)]
@@ -112,28 +104,6 @@ def peptide_backbone_torsions(z, bonds):
         phi += mine_phi
         psi += mine_psi
     return phi, psi, pairs
-
-
-def _peptide_residues(z, nbrs):
-    """The rule of ``peptide_backbone_torsions``: ``(is_amide [n], [(N, CA, C), ...])`` in the order of N, then of its
-    neighbours CA, then of CA's neighbours C (``tica.backbone_atoms`` selects the same atoms)."""
-    n = z.shape[0]
-
-    def amide(c):
-        if z[c] != 6:
-            return False
-        carbonyl = [o for o in nbrs[c] if z[o] == 8 and len(nbrs[o]) == 1]
-        return len(carbonyl) == 1 and any(z[a] == 7 for a in nbrs[c])
-    is_amide = [amide(c) for c in range(n)]
-    residues = []
-    for N in range(n):
-        if z[N] != 7:
-            continue
-        for CA in nbrs[N]:
-            if z[CA] != 6 or is_amide[CA]:
-                continue
-            residues += [(N, CA, C) for C in nbrs[CA] if is_amide[C] and C != N]
-    return is_amide, residues
 
 
 def backbone_pairs(coords: InternalCoords, z, bonds) -> Tuple[InternalCoords, List[Tuple[int, int]]]:
@@ -147,8 +117,7 @@ def backbone_pairs(coords: InternalCoords, z, bonds) -> Tuple[InternalCoords, Li
 
 # ----------------------------------------------------------------------------- the launch
 def limits() -> Dict[str, int]:
-    lib = _lib.load()
-    return {k: int(getattr(lib, "cgv_internal_hist_max_" + k)()) for k in ("features", "pairs", "bins", "bins2", "atoms", "staged_atoms")}
+    return ensemble.limits("internal_hist", ("features", "pairs", "bins", "bins2", "atoms", "staged_atoms"))
 
 
 class _DeviceTable:
@@ -184,7 +153,6 @@ def histograms(xyz, coords: InternalCoords, n_bins: int = 36, n_bins2: int = 36,
     ``xyz [S,n,3]`` (a host array, or a tensor on any device -- a device tensor decides the device).  One launch per
     ``structures_per_launch`` structures into int32 counts, added to int64 totals after every launch (a slot of one launch
     holds at most its structure count); ONE read-back per call."""
-    from .evaluate import _read_back
     lim = limits()
     if coords.n_features > lim["features"] or coords.n_pairs > lim["pairs"]:
         raise ValueError(f"{coords.n_features} features / {coords.n_pairs} pairs in one launch (the kernel holds "
@@ -198,7 +166,7 @@ def histograms(xyz, coords: InternalCoords, n_bins: int = 36, n_bins2: int = 36,
         raise ValueError(f"xyz must be [structures, {coords.n_atoms}, 3], got {tuple(x.shape)}")
     if coords.n_atoms > lim["atoms"]:
         raise ValueError(f"{coords.n_atoms} atoms per structure (the kernel holds {lim['atoms']})")
-    dev = x.device if x.is_cuda else torch.device(device)
+    dev = device_of(x, device)
     M = max(int(structures_per_launch), 1)
     table = _DeviceTable(coords, dev)
     shape, shape2 = (coords.n_features, n_bins + 3), (coords.n_pairs, n_bins2, n_bins2)
@@ -211,7 +179,7 @@ def histograms(xyz, coords: InternalCoords, n_bins: int = 36, n_bins2: int = 36,
         internal_hist(chunk, table, n_bins, n_bins2, bond_range, part, part2)
         total += part
         total2 += part2
-    counts, pair_counts = _read_back([total, total2])
+    counts, pair_counts = read_back([total, total2])
     return {"counts": counts, "pair_counts": pair_counts}
 
 
@@ -236,7 +204,6 @@ def feature_values(xyz, coords: InternalCoords, rows=None, structures_per_launch
     all, ``F = Nf``), computed by the device function that K15 bins with.  An invalid item (a non-finite coordinate, an
     atom outside the structure) is NaN; ``return_invalid=True`` also returns their number.  One launch per
     ``structures_per_launch`` structures, ONE read-back."""
-    from .evaluate import _read_back
     lim = limits()
     sub = coords
     if rows is not None:
@@ -252,7 +219,7 @@ def feature_values(xyz, coords: InternalCoords, rows=None, structures_per_launch
         raise ValueError(f"xyz must be [structures, {coords.n_atoms}, 3], got {tuple(x.shape)}")
     if not 1 <= coords.n_atoms <= lim["atoms"]:
         raise ValueError(f"{coords.n_atoms} atoms per structure (the kernel holds 1..{lim['atoms']})")
-    dev = x.device if x.is_cuda else torch.device(device)
+    dev = device_of(x, device)
     M = max(int(structures_per_launch), 1)
     table = _DeviceTable(sub, dev)
     values = torch.empty((int(x.shape[0]), sub.n_features), dtype=torch.float64, device=dev)
@@ -260,32 +227,12 @@ def feature_values(xyz, coords: InternalCoords, rows=None, structures_per_launch
     for start in range(0, int(x.shape[0]), M):
         chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
         internal_values(chunk, table, values[start:start + M], n_invalid)
-    out, bad = _read_back([values, n_invalid])
+    out, bad = read_back([values, n_invalid])
     return (out, int(bad[0])) if return_invalid else out
 
 
 # ----------------------------------------------------------------------------- host statistics
 UNDER, OVER, INVALID = 0, -2, -1         # slots of a feature's row next to its bins [1 : -2]
-
-
-def js_divergence(counts_a, counts_b) -> Optional[float]:
-    """Jensen-Shannon divergence, base 2 (in [0, 1]), of two histograms given as integer counts over the same bins (any
-    shape; a feature's row without its under / over / invalid slots, or a pair's ``[n_bins2, n_bins2]`` map).  fp64.
-    Bins empty in both are skipped.  ``None`` when either histogram is empty: there is no distribution to compare."""
-    a = np.asarray(counts_a, dtype=np.float64).reshape(-1)
-    b = np.asarray(counts_b, dtype=np.float64).reshape(-1)
-    if a.shape != b.shape:
-        raise ValueError("the histograms have different bins")
-    na, nb = a.sum(), b.sum()
-    if na <= 0 or nb <= 0:
-        return None
-    keep = (a > 0) | (b > 0)
-    p, q = a[keep] / na, b[keep] / nb
-    m = 0.5 * (p + q)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        kl_p = np.where(p > 0, p * np.log2(p / m), 0.0).sum()
-        kl_q = np.where(q > 0, q * np.log2(q / m), 0.0).sum()
-    return float(min(max(0.5 * (kl_p + kl_q), 0.0), 1.0))
 
 
 def outside(row) -> Dict[str, int]:

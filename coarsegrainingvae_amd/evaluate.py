@@ -10,6 +10,8 @@ into the reference's tuples -- pure functions of those outputs (``assemble_*``),
 Everything runs under ``torch.no_grad()`` and leaves ``model.training`` as it found it; the device generator of
 ``ops.reparam_sample`` advances when latents are drawn (``ops.get_sample_rng_state`` / ``set_sample_rng_state`` to
 bracket an evaluation inside a training run).
+
+``read_back``, the one device-to-host copy every analysis ends with, lives in ``ensemble`` with what else they share.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import torch
 
 from . import _lib
 from .data import CG_collate, prepare_batch
+from .ensemble import read_back
 from .graph import BatchGraph, cutoff_threshold_sq
 
 # Covalent radii in Angstrom behind the bond cutoffs (r_a + r_b) * scale: the CSD legacy covalent radii as published
@@ -283,20 +286,7 @@ class _quiet_empty_mean:
 
 
 # ----------------------------------------------------------------------------- device plumbing
-def _read_back(tensors: Sequence[torch.Tensor]) -> List[np.ndarray]:
-    """ONE device-to-host copy for a set of tensors (widest element type first, so every piece stays aligned)."""
-    order = sorted(range(len(tensors)), key=lambda i: -tensors[i].element_size())
-    flat = torch.cat([tensors[i].detach().contiguous().reshape(-1).view(torch.uint8) for i in order]).cpu()
-    out, at = [None] * len(tensors), 0
-    for i in order:
-        t = tensors[i]
-        nbytes = t.numel() * t.element_size()
-        out[i] = flat[at:at + nbytes].view(t.dtype).reshape(t.shape).numpy()
-        at += nbytes
-    return out
-
-
-def _settle(model):
+def settle(model):
     """A deferred parameter update of the trainer may still run on its side stream (``CGequiVAE.before_decoder``): wait
     for it before the decoder's weights are read outside ``model.forward``."""
     hook = getattr(model, "before_decoder", None)
@@ -316,7 +306,7 @@ def _mirrored(frame: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-def _device_of(model) -> torch.device:
+def model_device(model) -> torch.device:
     return next(model.parameters()).device
 
 
@@ -387,11 +377,11 @@ def sample_ensemble(dataset_or_loader, model, n_sample: int, reflection: bool = 
     frames = _as_frames(dataset_or_loader)
     if reflection:
         frames = [_mirrored(f) for f in frames]
-    dev = _device_of(model)
+    dev = model_device(model)
     sample_l, data_l, cg_l, recon_l, per_frame = [], [], [], [], []
     eps_at = 0
     with torch.no_grad():
-        _settle(model)
+        settle(model)
         for start in range(0, len(frames), max(int(frames_per_launch), 1)):
             chunk = frames[start:start + max(int(frames_per_launch), 1)]
             sizes = [int(f["nxyz"].shape[0]) for f in chunk]
@@ -418,7 +408,7 @@ def sample_ensemble(dataset_or_loader, model, n_sample: int, reflection: bool = 
                 out += [raw.counts, raw.sums]
             recon = model(batch)[5]
             out.append(recon)
-            host = _read_back(out)
+            host = read_back(out)
             a0 = b0 = 0
             for f, (n, nb) in enumerate(zip(sizes, beads)):
                 sample_l.append(host[0][K * a0:K * (a0 + n)])
@@ -448,7 +438,7 @@ def eval_sample_qualities(ref_xyz, gen_xyzs, z, scale: float = 1.3, radii: Optio
     n, K = int(ref.shape[0]), int(gen.shape[0])
     plan = QualityPlan(z, [0, n], device, scale, radii, thresholds)
     raw = sample_quality(ref.to(device), gen.reshape(K * n, 3).to(device), n_samples=K, plan=plan)
-    counts, sums = _read_back([raw.counts, raw.sums])
+    counts, sums = read_back([raw.counts, raw.sums])
     return assemble_sample_qualities(counts[0], sums[0], n, int(plan.n_heavy[0]))
 
 
@@ -459,17 +449,17 @@ def reconstruction_quality(batches: Iterable[Dict[str, torch.Tensor]], model, re
     the four statistics being means over frames of the one-sample evaluation ``reconstruction vs frame``.  The metric is
     the same kernel with ``n_samples = 1``; per batch one forward, one metric launch, one read-back.  Like the reference
     it evaluates in ``model.eval()``; the mode found is restored.  ``reflection`` mirrors y first, on copies."""
-    dev = _device_of(model)
+    dev = model_device(model)
     was_training = model.training
     model.eval()
     true_l, recon_l, cg_l, per_frame = [], [], [], []
     try:
         with torch.no_grad():
-            _settle(model)
+            settle(model)
             for batch in batches:
                 if reflection:
                     batch = _mirrored(batch)
-                z_host, sizes = _read_back([batch["nxyz"][:, 0], batch["num_atoms"]]) if batch["nxyz"].is_cuda else \
+                z_host, sizes = read_back([batch["nxyz"][:, 0], batch["num_atoms"]]) if batch["nxyz"].is_cuda else \
                     (batch["nxyz"][:, 0].numpy(), batch["num_atoms"].numpy())
                 if "_graph" not in batch:
                     batch = prepare_batch(dict(batch), dev)
@@ -477,7 +467,7 @@ def reconstruction_quality(batches: Iterable[Dict[str, torch.Tensor]], model, re
                 recon = model(batch)[5]
                 plan = QualityPlan(z_host, np.concatenate([[0], np.cumsum(_host_ints(sizes))]), dev, scale, radii)
                 raw = sample_quality(graph.xyz, recon, n_samples=1, plan=plan)
-                xyz_h, recon_h, cg_h, counts, sums = _read_back([graph.xyz, recon, graph.cg_xyz, raw.counts, raw.sums])
+                xyz_h, recon_h, cg_h, counts, sums = read_back([graph.xyz, recon, graph.cg_xyz, raw.counts, raw.sums])
                 true_l.append(xyz_h), recon_l.append(recon_h), cg_l.append(cg_h)
                 for f in range(plan.n_frames):
                     per_frame.append(assemble_sample_qualities(counts[f], sums[f], int(plan.sizes[f]), int(plan.n_heavy[f])))

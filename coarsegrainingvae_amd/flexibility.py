@@ -17,6 +17,8 @@ structure resembles, and RMSF measures the spread BETWEEN the states as much as 
 still comparable between data and model -- the same chimera, the same spread, when the model populates the states as the
 data does -- and ``coverage`` and ``tica`` are what tells the states apart.  RMSF also depends on the selection the
 superposition is fitted on: compare profiles only for the same selection.
+
+The host pieces shared with the other analyses (``selection``, ``groups_of``, ``scalar_block``, ...) live in ``ensemble``.
 """
 from __future__ import annotations
 
@@ -25,30 +27,15 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, options
-from .coverage import _structures, select_atoms
+from . import _lib, ensemble, options
+from .coverage import rmsd_matrix
+from .ensemble import check_sets, device_of, groups_of, read_back, scalar_block, select_atoms, structures
 
 WORKSPACE_BYTES = 1 << 28              # structures_per_launch is lowered until the partial sums of a launch fit this
 
 
 def limits() -> Dict[str, int]:
-    lib = _lib.load()
-    return {k: int(getattr(lib, "cgv_align_max_" + k)()) for k in ("structures", "atoms")}
-
-
-def _check_sel(sel, n_atoms: int, at_least: int = 1) -> np.ndarray:
-    """The selection as the kernel takes it (int32 ``[m]``; default: every atom); ``ValueError`` before any launch for an
-    empty selection, fewer than ``at_least`` atoms, an index outside ``[0, n_atoms)`` or an atom named twice."""
-    s = np.arange(n_atoms, dtype=np.int64) if sel is None else np.asarray(sel, dtype=np.int64).reshape(-1)
-    if s.shape[0] == 0:
-        raise ValueError("the selection is empty (m = 0): no atoms to superpose")
-    if s.shape[0] < at_least:
-        raise ValueError(f"the selection lists {s.shape[0]} atoms: a rotation needs at least {at_least}")
-    if s.min() < 0 or s.max() >= n_atoms:
-        raise ValueError(f"the selection names atom {int(s.max() if s.max() >= n_atoms else s.min())}, a structure has {n_atoms} atoms")
-    if np.unique(s).shape[0] != s.shape[0]:
-        raise ValueError("the selection names an atom twice")
-    return np.ascontiguousarray(s.astype(np.int32))
+    return ensemble.limits("align")
 
 
 def _form(n_atoms: int) -> int:
@@ -102,7 +89,7 @@ def align_accumulate(xyz: torch.Tensor, sel: torch.Tensor, ref: torch.Tensor, su
         return
     need = int(_lib.load().cgv_align_workspace_bytes(S, n, form))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=xyz.device)
+        workspace = ensemble.workspace(need, xyz.device)
     _lib.call("cgv_align_accumulate", _lib.ptr(xyz), _lib.ptr(sel), _lib.ptr(ref), S, n, m, form, _lib.ptr(sum), _lib.ptr(dev2),
               _lib.ptr(n_good), _lib.ptr(rmsd2), _lib.ptr(bad), _lib.ptr(aligned), _lib.ptr(workspace),
               workspace.numel() * workspace.element_size(), _lib.stream_ptr(), tag="align_accumulate")
@@ -112,16 +99,16 @@ class _Passes:
     """The structures of one set on the device, cut into launches, and the buffers every pass reuses."""
 
     def __init__(self, xyz, sel, structures_per_launch, device):
-        x = _structures(xyz)
+        x = structures(xyz)
         self.S, self.n = int(x.shape[0]), int(x.shape[1])
         lim = limits()
         if self.n < 1 or self.n > lim["atoms"]:
             raise ValueError(f"{self.n} atoms per structure (the kernel holds 1..{lim['atoms']})")
         if self.S >= 2 ** 31:
             raise ValueError("n_good is int32: fewer than 2^31 structures")
-        self.table = _check_sel(sel, self.n, at_least=3)
+        self.table = ensemble.selection(sel, self.n, purpose="superpose", at_least=3)
         self.form = _form(self.n)
-        self.dev = x.device if x.is_cuda else torch.device(device)
+        self.dev = device_of(x, device)
         if int(structures_per_launch) < 1:
             raise ValueError("structures_per_launch must be at least 1")
         self.M = max(1, min(int(structures_per_launch), lim["structures"]))
@@ -132,7 +119,7 @@ class _Passes:
         self.sel = torch.from_numpy(self.table).to(self.dev)
         self.sel64 = self.sel.long()
         need = int(lib.cgv_align_workspace_bytes(min(self.M, max(self.S, 1)), self.n, self.form))
-        self.ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.dev)
+        self.ws = ensemble.workspace(need, self.dev)
         self.rmsd2 = torch.zeros(self.S, dtype=torch.float64, device=self.dev)
         self.bad = torch.zeros(self.S, dtype=torch.int32, device=self.dev)
 
@@ -169,7 +156,6 @@ def mean_structure(xyz, sel=None, max_iter: int = 10, tol: float = 1e-4, structu
     ``mean`` and ``rmsf`` are ``None`` when no structure is good.  The order of every addition is fixed: the same call
     gives the same bits.  ONE read-back at the end, and one scalar per pass (the move).  Limits (``limits()``) and bad
     arguments are refused before any launch."""
-    from .evaluate import _read_back
     if int(max_iter) < 1 or not float(tol) >= 0:
         raise ValueError("max_iter must be at least 1 and tol a number >= 0")
     p = _Passes(xyz, sel, structures_per_launch, device)
@@ -194,7 +180,7 @@ def mean_structure(xyz, sel=None, max_iter: int = 10, tol: float = 1e-4, structu
     mean = state["sum"] / state["n_good"].double()
     shift = mean - p.centred(target)
     msf = torch.clamp(state["dev2"] / state["n_good"].double() - (shift * shift).sum(1), min=0.0)
-    mean_h, msf_h, rmsd2, bad, good = _read_back([mean, msf, p.rmsd2, p.bad, state["n_good"]])
+    mean_h, msf_h, rmsd2, bad, good = read_back([mean, msf, p.rmsd2, p.bad, state["n_good"]])
     return {"mean": mean_h, "rmsf": np.sqrt(msf_h), "rmsd": np.sqrt(rmsd2), "bad": bad.astype(bool), "n_good": int(good[0]),
             "iterations": passes + 1, "converged": converged, "last_move": move}
 
@@ -203,31 +189,40 @@ def aligned(xyz, mean, sel=None, structures_per_launch: int = 4096, device="cuda
     """The structures ``xyz [S,n,3]`` superposed onto ``mean [n,3]`` over ``sel`` -- every atom rotated, in the frame in
     which the mean's selected atoms have their centroid at the origin -- as a host array ``[S,n,3]`` fp32 (NaN rows: bad
     structures).  One pass, one read-back."""
-    from .evaluate import _read_back
     p = _Passes(xyz, sel, structures_per_launch, device)
     target = torch.as_tensor(np.ascontiguousarray(np.asarray(mean, dtype=np.float64))).to(p.dev)
     if tuple(target.shape) != (p.n, 3):
         raise ValueError(f"mean must be [{p.n}, 3], got {tuple(target.shape)}")
     out = torch.empty(p.S, p.n, 3, dtype=torch.float32, device=p.dev)
     p.run(target, aligned=out)
-    return _read_back([out])[0]
+    return read_back([out])[0]
 
 
 # ----------------------------------------------------------------------------- host statistics
-def group_profile(rmsf, sel, labels=None):
-    """``(rows, profile)``: without ``labels`` the RMSF of the selected atoms, rows = their indices; with ``labels [m]``
-    (a group per selected atom) per group the root of the mean of its atoms' mean-square fluctuations, rows = the labels
-    in ascending order."""
+def group_rows(sel, labels=None):
+    """``(rows, dense)``: what a row of a profile over the selection ``sel`` is -- without ``labels`` the atom indices
+    (``dense`` is ``None``), with ``labels [m]`` (a group per selected atom) the labels in ascending order and, per
+    selected atom, the row of its group."""
     sel = np.asarray(sel, dtype=np.int64).reshape(-1)
-    r = np.asarray(rmsf, dtype=np.float64)[sel]
     if labels is None:
-        return [int(i) for i in sel], r
+        return [int(i) for i in sel], None
     lab = np.asarray(labels, dtype=np.int64).reshape(-1)
     if lab.shape[0] != sel.shape[0]:
         raise ValueError(f"labels lists {lab.shape[0]} atoms, the selection {sel.shape[0]}")
     ids, dense = np.unique(lab, return_inverse=True)
-    msf = np.bincount(dense, weights=r * r, minlength=ids.shape[0]) / np.bincount(dense, minlength=ids.shape[0])
-    return [int(i) for i in ids], np.sqrt(msf)
+    return [int(i) for i in ids], dense
+
+
+def group_profile(rmsf, sel, labels=None):
+    """``(rows, profile)``: without ``labels`` the RMSF of the selected atoms, rows = their indices; with ``labels [m]``
+    (a group per selected atom) per group the root of the mean of its atoms' mean-square fluctuations, rows = the labels
+    in ascending order (``group_rows``)."""
+    rows, dense = group_rows(sel, labels)
+    r = np.asarray(rmsf, dtype=np.float64)[np.asarray(sel, dtype=np.int64).reshape(-1)]
+    if dense is None:
+        return rows, r
+    msf = np.bincount(dense, weights=r * r, minlength=len(rows)) / np.bincount(dense, minlength=len(rows))
+    return rows, np.sqrt(msf)
 
 
 def _profile_stats(a, b) -> dict:
@@ -244,7 +239,6 @@ def _profile_stats(a, b) -> dict:
 
 
 def _mean_rmsd(a: dict, b: dict, sel, device) -> Optional[float]:
-    from .coverage import rmsd_matrix
     if a["mean"] is None or b["mean"] is None:
         return None
     return float(rmsd_matrix(a["mean"][None].astype(np.float32), b["mean"][None].astype(np.float32), sel, device=device)[0, 0])
@@ -255,7 +249,7 @@ def compare(ref_xyz, gen_xyz, z, bonds, atoms="heavy", groups=None, mapping=None
     """Generated structures ``gen_xyz [Sg,n,3]`` against reference frames ``ref_xyz [Sr,n,3]`` (at least two) of the
     molecule ``z [n]`` / ``bonds [Eb,2]`` by their flexibility: each set is superposed about ITS OWN mean structure over
     ``select_atoms(z, atoms)`` (at least three atoms) and the RMSF profiles are compared.  ``groups``: ``None`` (a row per
-    selected atom), ``"bead"`` (needs ``mapping``) or ``"residue"`` (``contacts.groups_of``): a row per group, the root of
+    selected atom), ``"bead"`` (needs ``mapping``) or ``"residue"`` (``ensemble.groups_of``): a row per group, the root of
     the mean of its selected atoms' mean-square fluctuations.  The convention of ``distributions.compare`` and
     ``contacts.compare``: the even and the odd reference frames are also analysed apart, and what the two halves differ
     by is the ``floor`` every deviation is to be read against.  Returns a dict that ``json.dump`` takes:
@@ -273,17 +267,9 @@ def compare(ref_xyz, gen_xyz, z, bonds, atoms="heavy", groups=None, mapping=None
       convergence   {ref, gen, even, odd}: {iterations, converged, last_move} of each ``mean_structure``
       top_atoms     the ten rows of largest |rmsf_gen - rmsf_ref|: {label, rmsf_ref, rmsf_gen}
     """
-    from .contacts import groups_of
-    ref, gen = _structures(ref_xyz), _structures(gen_xyz)
-    z = np.asarray(z).astype(np.int64).reshape(-1)
-    if int(ref.shape[0]) < 2:
-        raise ValueError("at least two reference frames are needed (the floor compares the even with the odd ones)")
-    if z.shape[0] != int(ref.shape[1]) or int(gen.shape[1]) != int(ref.shape[1]):
-        raise ValueError(f"z lists {z.shape[0]} atoms, the frames have {int(ref.shape[1])} and {int(gen.shape[1])}")
-    if groups not in (None, "bead", "residue"):
-        raise ValueError("groups must be None, 'bead' or 'residue'")
+    ref, gen, z = check_sets(ref_xyz, gen_xyz, z, groups=groups)
     sel = select_atoms(z, atoms)
-    _check_sel(sel, z.shape[0], at_least=3)
+    ensemble.selection(sel, z.shape[0], purpose="superpose", at_least=3)
     glab = None if groups is None else groups_of(z, bonds, mapping, groups)[sel]
     kw = dict(sel=sel, max_iter=max_iter, tol=tol, structures_per_launch=structures_per_launch, device=device)
     runs = {"ref": mean_structure(ref, **kw), "gen": mean_structure(gen, **kw),
@@ -299,9 +285,8 @@ def compare_from_runs(runs: dict, sel, group_labels=None, mean_rmsd=None, floor_
     ``"gen"``, ``"even"`` and ``"odd"`` (the reference's halves), all over the selection ``sel`` -- pure host.
     ``group_labels [m]``: a group per selected atom (``None``: a row per atom); ``mean_rmsd`` / ``floor_mean_rmsd``: the
     superposed RMSD between the means of ref and gen / of even and odd, which ``compare`` takes from K17."""
-    from .contacts import _scalar_block
     sel = np.asarray(sel, dtype=np.int64).reshape(-1)
-    labels = group_profile(np.zeros(int(sel.max()) + 1), sel, group_labels)[0]
+    labels = group_rows(sel, group_labels)[0]
     prof = {k: None if r["rmsf"] is None else group_profile(r["rmsf"], sel, group_labels)[1] for k, r in runs.items()}
     stats = _profile_stats(prof["ref"], prof["gen"])
     floor = dict(_profile_stats(prof["even"], prof["odd"]), mean_rmsd=floor_mean_rmsd)
@@ -310,7 +295,7 @@ def compare_from_runs(runs: dict, sel, group_labels=None, mean_rmsd=None, floor_
     fin = lambda v: v[np.isfinite(v)]
     if fin(r_ref).size and fin(r_gen).size:
         hi = 1.2 * float(fin(r_ref).max())
-        block = _scalar_block(fin(r_ref[0::2]), fin(r_ref[1::2]), fin(r_gen), 0.0, hi if hi > 0 else 1.0, n_bins)
+        block = scalar_block(fin(r_ref[0::2]), fin(r_ref[1::2]), fin(r_gen), 0.0, hi if hi > 0 else 1.0, n_bins)
     if prof["ref"] is not None and prof["gen"] is not None:
         dev = np.abs(prof["gen"] - prof["ref"])
         for k in np.argsort(-dev, kind="stable")[:10]:

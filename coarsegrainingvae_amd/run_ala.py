@@ -45,8 +45,9 @@ from datetime import date
 import numpy as np
 import torch
 
-from . import cgmap
+from . import cgmap, contacts, coverage, density, distributions, flexibility, tica
 from . import data as cgdata
+from .analyses import ANALYSES, BY_STEM
 from .train import build_model, optim_dict
 from .trainer import Trainer
 
@@ -136,10 +137,7 @@ def build_extras_parser() -> argparse.ArgumentParser:
 def stored_params(params: dict) -> dict:
     """What ``modelparams.json`` records of the parameters: a switch of ``build_extras_parser`` that is off leaves the
     file as it was before the switch existed (its key, and the keys of its options, are left out)."""
-    off = [k for k, switch in (("dist_eval", "dist_eval"), ("tica_eval", "tica_eval"), ("tica_lag", "tica_eval"),
-                               ("cov_eval", "cov_eval"), ("contact_eval", "contact_eval"), ("flex_eval", "flex_eval"),
-                               ("kde_eval", "kde_eval"))
-           if not params.get(switch)]
+    off = [k for a in ANALYSES if not params.get(a.stem + "_eval") for k in (a.stem + "_eval",) + a.options]
     return {k: v for k, v in params.items() if k not in off}
 
 
@@ -305,123 +303,83 @@ def evaluate_run(params, model, dataset, train_idx, val_idx, device, last_epoch,
         if samples is not None and isinstance(samples[0], np.ndarray):
             np.savez_compressed(os.path.join(logdir, "samples.npz"), sample_xyzs=samples[0], data_xyzs=samples[1],
                                 cg_xyzs=samples[2], recon_xyzs=samples[3], n_ensemble=params["n_ensemble"])
-    if params.get("dist_eval"):
-        stats["dist_stats"] = dist_eval(dataset, val_idx, samples, device, logdir)
-    if params.get("tica_eval"):
-        stats["tica_stats"] = tica_eval(params, dataset, val_idx, samples, device, logdir)
-    if params.get("cov_eval"):
-        stats["cov_stats"] = cov_eval(dataset, val_idx, samples, device, logdir)
-    if params.get("contact_eval"):
-        stats["contact_stats"] = contact_eval(dataset, val_idx, samples, device, logdir)
-    if params.get("flex_eval"):
-        stats["flex_stats"] = flex_eval(dataset, val_idx, samples, device, logdir)
-    if params.get("kde_eval"):
-        stats["kde_stats"] = kde_eval(dataset, val_idx, samples, device, logdir)
+    for a in ANALYSES:
+        if params.get(a.stem + "_eval"):
+            head = (params,) if a.options else ()                         # an analysis with options reads them there
+            stats[a.stem + "_stats"] = globals()[a.stem + "_eval"](*head, dataset, val_idx, samples, device, logdir)
     return stats
 
 
-def dist_eval(dataset, val_idx, samples, device, logdir):
-    """``--dist_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
-    tuple), over the internal coordinates of the molecule's bond graph.  Writes ``dist_stats.json``; returns the means
-    (``distributions.summary_of``), or ``None`` when there is nothing to compare (fewer than two hold-out frames, or
-    frames of different molecules)."""
-    from . import distributions
-    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
-        print("--dist_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
+def _finish(a, full, logdir):
+    """The full statistics of analysis ``a`` go to ``<stem>_stats.json`` in the log directory, their short form to the caller."""
+    if logdir:
+        with open(os.path.join(logdir, a.stem + "_stats.json"), "w") as f:
+            json.dump(full, f)
+    return a.module.summary_of(full)
+
+
+def _hold_out_eval(stem, compare, dataset, val_idx, samples, logdir):
+    """What ``--<stem>_eval`` does for every analysis of the hold-out frames against their prior samples (``samples``:
+    ``evaluate.sample_ensemble``'s tuple): ``compare(ref, gen, z, bonds)`` gives the full statistics, or ``None`` after
+    saying on stderr why it skipped.  Writes ``<stem>_stats.json``; returns the module's ``summary_of``, or ``None`` when
+    there is nothing to compare (too few hold-out frames, or frames of different molecules)."""
+    a = BY_STEM[stem]
+    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < a.min_frames:
+        print(f"--{stem}_eval skipped: it needs at least {'two' if a.min_frames == 2 else 'four'} hold-out frames of one molecule",
+              file=sys.stderr, flush=True)
         return None
     frame = dataset[val_idx[0]]
     z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
-    full = distributions.compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy(), device=device)
-    if logdir:
-        with open(os.path.join(logdir, "dist_stats.json"), "w") as f:
-            json.dump(full, f)
-    return distributions.summary_of(full)
+    full = compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy() if a.needs_bonds else None)
+    return None if full is None else _finish(a, full, logdir)
+
+
+def dist_eval(dataset, val_idx, samples, device, logdir):
+    """``--dist_eval``: over the internal coordinates of the molecule's bond graph (``distributions.compare``)."""
+    return _hold_out_eval("dist", lambda ref, gen, z, bonds: distributions.compare(ref, gen, z, bonds, device=device),
+                          dataset, val_idx, samples, logdir)
 
 
 def cov_eval(dataset, val_idx, samples, device, logdir):
-    """``--cov_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
-    tuple) by superposed heavy-atom RMSD: does every hold-out frame have a sample near it, is every sample near a hold-out
-    frame.  Writes ``cov_stats.json``; returns ``coverage.summary_of``, or ``None`` when there is nothing to compare
-    (fewer than two hold-out frames, or frames of different molecules)."""
-    from . import coverage
-    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
-        print("--cov_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
-        return None
-    frame = dataset[val_idx[0]]
-    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
-    atoms = "heavy" if (z != 1).any() else "all"
-    full = coverage.compare(samples[1], samples[0].reshape(-1, n, 3), z, atoms=atoms, device=device)
-    if logdir:
-        with open(os.path.join(logdir, "cov_stats.json"), "w") as f:
-            json.dump(full, f)
-    return coverage.summary_of(full)
+    """``--cov_eval``: by superposed heavy-atom RMSD (``coverage.compare``): does every hold-out frame have a sample near
+    it, is every sample near a hold-out frame."""
+    def compare(ref, gen, z, bonds):
+        return coverage.compare(ref, gen, z, atoms="heavy" if (z != 1).any() else "all", device=device)
+    return _hold_out_eval("cov", compare, dataset, val_idx, samples, logdir)
 
 
 def contact_eval(dataset, val_idx, samples, device, logdir):
-    """``--contact_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
-    tuple) by the contacts of their heavy atoms: contact probability maps, native contacts, Rg.  Writes
-    ``contact_stats.json``; returns ``contacts.summary_of``, which stays in the summary's ``"test_stats"``, or ``None``
-    when there is nothing to compare (fewer than two hold-out frames, or frames of different molecules)."""
-    from . import contacts
-    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
-        print("--contact_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
-        return None
-    frame = dataset[val_idx[0]]
-    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
-    atoms = "heavy" if (z != 1).sum() >= 2 else "all"
-    full = contacts.compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy(), atoms=atoms, device=device)
-    if logdir:
-        with open(os.path.join(logdir, "contact_stats.json"), "w") as f:
-            json.dump(full, f)
-    return contacts.summary_of(full)
+    """``--contact_eval``: by the contacts of their heavy atoms (``contacts.compare``): contact probability maps, native
+    contacts, Rg.  The short form stays in the summary's ``"test_stats"``."""
+    def compare(ref, gen, z, bonds):
+        return contacts.compare(ref, gen, z, bonds, atoms="heavy" if (z != 1).sum() >= 2 else "all", device=device)
+    return _hold_out_eval("contact", compare, dataset, val_idx, samples, logdir)
 
 
 def flex_eval(dataset, val_idx, samples, device, logdir):
-    """``--flex_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
-    tuple) by the fluctuation of their heavy atoms about each set's own mean structure.  Writes ``flex_stats.json``;
-    returns ``flexibility.summary_of``, which stays in the summary's ``"test_stats"``, or ``None`` when there is nothing to
-    compare (fewer than two hold-out frames, frames of different molecules, or fewer than three atoms)."""
-    from . import flexibility
-    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 2:
-        print("--flex_eval skipped: it needs at least two hold-out frames of one molecule", file=sys.stderr, flush=True)
-        return None
-    frame = dataset[val_idx[0]]
-    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
-    atoms = "heavy" if (z != 1).sum() >= 3 else "all"
-    if n < 3:
-        print("--flex_eval skipped: fewer than three atoms, no rotation to fit", file=sys.stderr, flush=True)
-        return None
-    full = flexibility.compare(samples[1], samples[0].reshape(-1, n, 3), z, frame["bond_edge_list"].numpy(), atoms=atoms, device=device)
-    if logdir:
-        with open(os.path.join(logdir, "flex_stats.json"), "w") as f:
-            json.dump(full, f)
-    return flexibility.summary_of(full)
+    """``--flex_eval``: by the fluctuation of their heavy atoms about each set's own mean structure
+    (``flexibility.compare``); skipped also for fewer than three atoms.  The short form stays in ``"test_stats"``."""
+    def compare(ref, gen, z, bonds):
+        if z.shape[0] < 3:
+            print("--flex_eval skipped: fewer than three atoms, no rotation to fit", file=sys.stderr, flush=True)
+            return None
+        return flexibility.compare(ref, gen, z, bonds, atoms="heavy" if (z != 1).sum() >= 3 else "all", device=device)
+    return _hold_out_eval("flex", compare, dataset, val_idx, samples, logdir)
 
 
 def kde_eval(dataset, val_idx, samples, device, logdir):
-    """``--kde_eval``: the hold-out frames against their prior samples (``samples``: ``evaluate.sample_ensemble``'s
-    tuple) as kernel density estimates in every (phi, psi) plane of the backbone.  Writes ``kde_stats.json``; returns
-    ``density.summary_of``, which stays in the summary's ``"test_stats"``, or ``None`` when there is nothing to compare
-    (where ``--dist_eval`` has nothing, fewer than four hold-out frames, or a molecule without a peptide backbone)."""
-    from . import density, distributions
-    if samples is None or not isinstance(samples[0], np.ndarray) or len(val_idx) < 4:
-        print("--kde_eval skipped: it needs at least four hold-out frames of one molecule", file=sys.stderr, flush=True)
-        return None
-    frame = dataset[val_idx[0]]
-    z, n = frame["nxyz"][:, 0].numpy().astype(np.int64), int(frame["nxyz"].shape[0])
-    bonds = frame["bond_edge_list"].numpy()
-    if not distributions.peptide_backbone_torsions(z, bonds)[2]:
-        print("--kde_eval skipped: the molecule has no peptide backbone, so no (phi, psi) plane", file=sys.stderr, flush=True)
-        return None
-    try:
-        full = density.compare_torsions(samples[1], samples[0].reshape(-1, n, 3), z, bonds, device=device)
-    except ValueError as err:                                            # a torsion without spread, a kernel wider than period / 12
-        print(f"--kde_eval skipped: {err}", file=sys.stderr, flush=True)
-        return None
-    if logdir:
-        with open(os.path.join(logdir, "kde_stats.json"), "w") as f:
-            json.dump(full, f)
-    return density.summary_of(full)
+    """``--kde_eval``: as kernel density estimates in every (phi, psi) plane of the backbone (``density.compare_torsions``);
+    skipped also for a molecule without a peptide backbone.  The short form stays in ``"test_stats"``."""
+    def compare(ref, gen, z, bonds):
+        if not distributions.peptide_backbone_torsions(z, bonds)[2]:
+            print("--kde_eval skipped: the molecule has no peptide backbone, so no (phi, psi) plane", file=sys.stderr, flush=True)
+            return None
+        try:
+            return density.compare_torsions(ref, gen, z, bonds, device=device)
+        except ValueError as err:                                        # a torsion without spread, a kernel wider than period / 12
+            print(f"--kde_eval skipped: {err}", file=sys.stderr, flush=True)
+            return None
+    return _hold_out_eval("kde", compare, dataset, val_idx, samples, logdir)
 
 
 def tica_eval(params, dataset, val_idx, samples, device, logdir):
@@ -430,7 +388,6 @@ def tica_eval(params, dataset, val_idx, samples, device, logdir):
     tuple) compared with them.  Writes ``tica_stats.json``; returns ``tica.summary_of``, or ``None`` when there is
     nothing to compare: synthetic frames have no time order, the file is shorter than ``lag + 2`` frames, or the
     molecule has no peptide backbone."""
-    from . import tica
     lag = int(params.get("tica_lag", 100))
     if not params.get("traj"):
         print("--tica_eval skipped: synthetic frames have no time order (it needs -traj)", file=sys.stderr, flush=True)
@@ -448,10 +405,7 @@ def tica_eval(params, dataset, val_idx, samples, device, logdir):
               file=sys.stderr, flush=True)
         return None
     full = tica.compare(tica.split_segments(xyz, starts), samples[0].reshape(-1, xyz.shape[1], 3), z, bonds, lag=lag, device=device)
-    if logdir:
-        with open(os.path.join(logdir, "tica_stats.json"), "w") as f:
-            json.dump(full, f)
-    return tica.summary_of(full)
+    return _finish(BY_STEM["tica"], full, logdir)
 
 
 def run(params) -> dict:
@@ -586,12 +540,9 @@ def run(params) -> dict:
         test_stats = evaluate_run(params, model, dataset, train_idx, val_idx, device, log_rows[-1] if log_rows else None, logdir)
     if world > 1:
         torch.distributed.destroy_process_group()
-    dist = {"dist_stats": test_stats.pop("dist_stats", None) if test_stats else None} if params.get("dist_eval") else {}
-    if params.get("tica_eval"):
-        dist["tica_stats"] = test_stats.pop("tica_stats", None) if test_stats else None
-    if params.get("cov_eval"):
-        dist["cov_stats"] = test_stats.pop("cov_stats", None) if test_stats else None
-    return {**dist, "epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
+    top = {a.stem + "_stats": test_stats.pop(a.stem + "_stats", None) if test_stats else None
+           for a in ANALYSES if a.top_level and params.get(a.stem + "_eval")}
+    return {**top, "epochs": len(log_rows), "seconds": elapsed, "train_frames_per_s": frames_seen / max(elapsed, 1e-9),
             "final": log_rows[-1] if log_rows else None, "failed": failed, "skipped_steps": trainer.skipped_steps(),
             "graph_replays": trainer.replays, "test_stats": test_stats,
             **({"cg_mapping": {k: map_info[k] for k in CG_MAPPING_KEYS.get(map_info.get("method"), CG_PARTITION_KEYS)

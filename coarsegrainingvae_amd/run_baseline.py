@@ -175,7 +175,7 @@ def graph_quality(data, recon, z, radii):
     T, n = int(data.shape[0]), int(data.shape[1])
     plan = ev.QualityPlan(np.tile(z, T), np.arange(T + 1) * n, data.device, radii=radii)
     raw = ev.sample_quality(data.reshape(T * n, 3), recon.reshape(T * n, 3), n_samples=1, plan=plan)
-    counts, sums = ev._read_back([raw.counts, raw.sums])
+    counts, sums = ev.read_back([raw.counts, raw.sums])
     per_frame = [ev.assemble_sample_qualities(counts[f], sums[f], n, int(plan.n_heavy[f])) for f in range(T)]
     return tuple(float(v) for v in ev.assemble_reconstruction(per_frame))
 

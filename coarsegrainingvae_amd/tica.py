@@ -12,6 +12,9 @@ on the matrix cores, and ``fit_from_moments`` solves the symmetrised (reversible
 A feature is an fp32 distance, ``sqrt((dx*dx + dy*dy) + dz*dz)`` with every operation rounded, widened to fp64: a host
 restatement in ``numpy.float32`` holds the same bits.  Non-finite coordinates are not filtered: they propagate into the
 moments (and make the fit fail loudly), and count as ``outside`` in the projection's histogram.
+
+The host pieces shared with the other analyses (``adjacency``, ``peptide_residues``, ``js_divergence``, ``read_back``)
+live in ``ensemble``.
 """
 from __future__ import annotations
 
@@ -21,8 +24,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
-from .distributions import _adjacency, _peptide_residues, js_divergence
+from . import _lib, ensemble
+from .ensemble import adjacency, device_of, js_divergence, peptide_residues, read_back
 
 
 # ----------------------------------------------------------------------------- features
@@ -31,7 +34,7 @@ def backbone_atoms(z, bonds) -> np.ndarray:
     non-amide carbon on it, an amide carbon on that: element and connectivity only), sorted.  Empty for a molecule
     without a peptide backbone: callers then need an explicit ``sel``."""
     z = np.asarray(z).astype(np.int64).reshape(-1)
-    _, residues = _peptide_residues(z, _adjacency(z.shape[0], bonds))
+    _, residues = peptide_residues(z, adjacency(z.shape[0], bonds))
     return np.array(sorted({a for r in residues for a in r}), dtype=np.int64)
 
 
@@ -46,8 +49,7 @@ def distance_pairs(sel, excluded_neighbors: int = 2) -> np.ndarray:
 
 
 def limits() -> Dict[str, int]:
-    lib = _lib.load()
-    return {k: int(getattr(lib, "cgv_tica_max_" + k)()) for k in ("features", "atoms", "bins2", "components")}
+    return ensemble.limits("tica", ("features", "atoms", "bins2", "components"))
 
 
 def _check_pairs(pairs, n_atoms: int) -> np.ndarray:
@@ -66,7 +68,7 @@ def _check_pairs(pairs, n_atoms: int) -> np.ndarray:
     return p.astype(np.int32)
 
 
-def _frames(x) -> torch.Tensor:
+def frames(x) -> torch.Tensor:
     t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
     if t.dim() != 3 or t.shape[2] != 3:
         raise ValueError(f"frames must be [T, n, 3], got {tuple(t.shape)}")
@@ -101,7 +103,7 @@ def moments_launch(xyz: torch.Tensor, pairs: torch.Tensor, lag: int, totals: Dic
         raise ValueError("the totals do not have the shape of the pair table")
     need = int(_lib.load().cgv_tica_moments_workspace_bytes(T, d, int(lag)))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 7) // 8, dtype=torch.float64, device=xyz.device)
+        workspace = ensemble.workspace(need, xyz.device)
     _lib.call("cgv_tica_moments", _lib.ptr(xyz), _lib.ptr(pairs), T, n, d, int(lag), *[_lib.ptr(totals[k]) for k in MOMENT_KEYS],
               _lib.ptr(workspace), workspace.numel() * workspace.element_size(), _lib.stream_ptr(), tag="tica_moments")
     return max(T - int(lag), 0)
@@ -113,11 +115,10 @@ def moments(trajs: Sequence, pairs, lag: int, frames_per_launch: int = 65536, de
     ``sum(max(T_i - lag, 0))``.  A frame pair ``(t, t + lag)`` never crosses a segment boundary.  A segment with more
     than ``frames_per_launch`` pairs is fed as overlapping chunks ``[s, s + M + lag)``, so that every pair is counted
     exactly once.  The totals stay on the device in fp64 across the launches; ONE read-back."""
-    from .evaluate import _read_back
     lag, M = int(lag), max(int(frames_per_launch), 1)
     if lag < 1:
         raise ValueError("lag must be at least 1")
-    segs = [_frames(x) for x in trajs]
+    segs = [frames(x) for x in trajs]
     if not segs:
         raise ValueError("no trajectory segments")
     n = int(segs[0].shape[1])
@@ -130,8 +131,7 @@ def moments(trajs: Sequence, pairs, lag: int, frames_per_launch: int = 65536, de
     ptab = torch.from_numpy(table).to(dev)
     totals = {k: torch.zeros((d,) if k.startswith("sum") else (d, d), dtype=torch.float64, device=dev) for k in MOMENT_KEYS}
     longest = max(min(int(s.shape[0]), M + lag) for s in segs)
-    workspace = torch.empty((int(_lib.load().cgv_tica_moments_workspace_bytes(longest, d, lag)) + 7) // 8, dtype=torch.float64,
-                            device=dev)
+    workspace = ensemble.workspace(_lib.load().cgv_tica_moments_workspace_bytes(longest, d, lag), dev)
     count = 0
     for seg in segs:
         N = int(seg.shape[0]) - lag
@@ -139,7 +139,7 @@ def moments(trajs: Sequence, pairs, lag: int, frames_per_launch: int = 65536, de
             m = min(M, N - start)
             chunk = seg[start:start + m + lag].detach().to(dev, torch.float32).contiguous()
             count += moments_launch(chunk, ptab, lag, totals, workspace)
-    host = _read_back([totals[k] for k in MOMENT_KEYS])
+    host = read_back([totals[k] for k in MOMENT_KEYS])
     return {**{k: np.array(v) for k, v in zip(MOMENT_KEYS, host)}, "n_frame_pairs": int(count)}
 
 
@@ -245,8 +245,7 @@ def project(xyz, model: TicaModel, structures_per_launch: int = 16384, device="c
     ``structures_per_launch`` structures, ONE read-back.  ``hist = (comp_a, comp_b, n_bins2, (lo_a, hi_a), (lo_b, hi_b))``
     also gives the joint histogram of two components: the return value is then ``(ics, counts [nb,nb] int64, outside)``;
     with ``want_ics=False`` the components are neither stored nor read back (``ics`` is ``None``)."""
-    from .evaluate import _read_back
-    x = _frames(xyz)
+    x = frames(xyz)
     S, n, k = int(x.shape[0]), int(x.shape[1]), int(model.W.shape[1])
     table = _check_pairs(model.pairs, n)
     lim = limits()
@@ -256,7 +255,7 @@ def project(xyz, model: TicaModel, structures_per_launch: int = 16384, device="c
         raise ValueError(f"n_bins2 must be in 1..{lim['bins2']}")
     if hist is not None and not (float(hist[3][0]) < float(hist[3][1]) and float(hist[4][0]) < float(hist[4][1])):
         raise ValueError("histogram ranges must be (lo, hi) with lo < hi")
-    dev = x.device if x.is_cuda else torch.device(device)
+    dev = device_of(x, device)
     ptab = torch.from_numpy(table).to(dev)
     mean = torch.from_numpy(np.ascontiguousarray(model.mean, dtype=np.float64)).to(dev)
     W = torch.from_numpy(np.ascontiguousarray(model.W, dtype=np.float64)).to(dev)
@@ -278,7 +277,7 @@ def project(xyz, model: TicaModel, structures_per_launch: int = 16384, device="c
         if hist is not None:
             total += counts
             total_out += outside
-    back = _read_back(([ics] if want_ics else []) + ([total, total_out] if hist is not None else []))
+    back = read_back(([ics] if want_ics else []) + ([total, total_out] if hist is not None else []))
     out_ics = np.array(back[0]) if want_ics else None
     if hist is None:
         return out_ics
@@ -303,7 +302,7 @@ def compare(ref_trajs, gen_xyz, z, bonds, lag: int = 100, sel=None, excluded_nei
       counts       {ref, gen}: the maps [n_bins2][n_bins2] themselves
 
     A model of one component (rank 1) compares that component with itself: the map is its diagonal."""
-    segs = [_frames(x) for x in ref_trajs]
+    segs = [frames(x) for x in ref_trajs]
     z = np.asarray(z).astype(np.int64).reshape(-1)
     if sel is None:
         sel = backbone_atoms(z, bonds)
@@ -324,7 +323,7 @@ def compare(ref_trajs, gen_xyz, z, bonds, lag: int = 100, sel=None, excluded_nei
     hist = (ca, cb, int(n_bins2), ranges[0], ranges[1])
     _, even, out_even = project(ref[0::2], model, hist=hist, want_ics=False, **kw)
     _, odd, out_odd = project(ref[1::2], model, hist=hist, want_ics=False, **kw)
-    gen = _frames(gen_xyz)
+    gen = frames(gen_xyz)
     _, gen_counts, out_gen = project(gen, model, hist=hist, want_ics=False, **kw)
     whole = even + odd
     return {"n_ref": int(ref.shape[0]), "n_gen": int(gen.shape[0]), "n_frame_pairs": model.n_frame_pairs, "d": int(pairs.shape[0]),

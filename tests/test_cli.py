@@ -115,3 +115,71 @@ def test_cli_optimizer_sgd_runs_through_the_fused_step(tmp_path, capsys, monkeyp
                  "-cg_cutoff 9.5 -beta 0.05 -gamma 25.0 -dec_nconv 2 -enc_nconv 2 -lr 0.01 -n_basis 32 -n_rbf 8 -optimizer sgd --synthetic".split())
     summary = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert summary["epochs"] == 2 and not summary["failed"] and summary["graph_replays"] > 0
+
+
+# ----------------------------------------------------------------------------- every post-evaluation analysis at once
+# -edgeorder 1: the frames' bond list is the molecule's bonds alone, which is what finds the peptide backbone for --kde_eval
+ALL_SWITCHES_TRAIN = ("-device 0 -n_cgs 4 -ndata 64 -atom_cutoff 8.5 -cg_cutoff 9.5 -beta 0.05 -gamma 25.0 -lr 0.001 -edgeorder 1 "
+                      "-n_basis 32 -n_rbf 8 -enc_nconv 2 -dec_nconv 2 -nepochs 1 -batch_size 8 -n_ensemble 4")
+
+
+@pytest.fixture(scope="module")
+def all_switches_run(tmp_path_factory):
+    """``run_ala.main`` once, with all six ``--*_eval`` switches, on 64 frames of the three-residue peptide of
+    ``density_restatement`` (phi and psi narrow enough for a torsion's kernel to stay below period / 12 on the seven
+    hold-out frames): ``(run directory, trajectory file, summary line)``."""
+    import contextlib
+    import io
+    import math
+    import numpy as np
+    import density_restatement as R
+    from coarsegrainingvae_amd.analyses import ANALYSES
+    tmp = tmp_path_factory.mktemp("all_switches")
+    rng = np.random.default_rng(11)
+    torsions = np.full((64, 10), math.pi)                                 # omega_0, (phi, psi, omega) per residue
+    torsions[:, 1::3], torsions[:, 2::3] = rng.normal(-1.2, 0.25, (64, 3)), rng.normal(2.4, 0.25, (64, 3))
+    z, bonds = R.peptide(3)
+    np.savez(tmp / "traj.npz", xyz=R.peptide_structures(3, torsions), z=z, bonds=bonds, mapping=np.arange(z.shape[0]) * 4 // z.shape[0])
+    switches = " ".join(f"--{a.stem}_eval" for a in ANALYSES)
+    out = io.StringIO()
+    with contextlib.redirect_stdout(out):
+        run_ala.main(f"-logdir {tmp / 'run'} -traj {tmp / 'traj.npz'} {ALL_SWITCHES_TRAIN} -tica_lag 5 {switches}".split())
+    return next(tmp.glob("run_*_N4")), tmp / "traj.npz", json.loads(out.getvalue().strip().splitlines()[-1])
+
+
+def _stats_keys():
+    from coarsegrainingvae_amd import contacts, coverage, density, distributions, flexibility, tica
+    return {"dist": distributions.DIST_STATS_KEYS, "tica": tica.TICA_STATS_KEYS, "cov": coverage.COV_STATS_KEYS,
+            "contact": contacts.CONTACT_STATS_KEYS, "flex": flexibility.FLEX_STATS_KEYS, "kde": density.KDE_STATS_KEYS}
+
+
+@pytest.mark.gpu
+def test_run_ala_with_every_eval_switch_writes_six_files_and_places_six_summaries(all_switches_run):
+    from coarsegrainingvae_amd.analyses import ANALYSES
+    logdir, _traj, summary = all_switches_run
+    assert not summary["failed"] and summary["epochs"] == 1
+    for a in ANALYSES:
+        key = a.stem + "_stats"
+        stats = json.loads((logdir / (key + ".json")).read_text())
+        assert set(stats) == set(_stats_keys()[a.stem]), a.stem
+        top = a.stem in ("dist", "tica", "cov")                          # the others stay under "test_stats"
+        assert (key in summary) == top and (key in summary["test_stats"]) == (not top), a.stem
+        assert (summary if top else summary["test_stats"])[key] == a.module.summary_of(stats), a.stem
+    stored = json.loads((logdir / "modelparams.json").read_text())
+    assert all(stored[a.stem + "_eval"] is True for a in ANALYSES) and stored["tica_lag"] == 5
+
+
+@pytest.mark.gpu
+def test_backmap_with_every_stats_switch_writes_six_files_next_to_out(all_switches_run, tmp_path, capsys):
+    from coarsegrainingvae_amd import backmap
+    from coarsegrainingvae_amd.analyses import ANALYSES
+    logdir, traj, _summary = all_switches_run
+    switches = " ".join(f"--{a.stem}_stats" for a in ANALYSES)
+    backmap.main(f"-model {logdir} -traj {traj} -n_samples 4 -out {tmp_path / 'out.npz'} -tica_lag 5 -kde_grid 16 {switches}".split())
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["frames"] == 64 and line["samples"] == 256
+    for a in ANALYSES:
+        key = a.stem + "_stats"
+        stats = json.loads((tmp_path / (key + ".json")).read_text())
+        assert set(stats) == set(_stats_keys()[a.stem]) and stats["n_ref"] == 64, a.stem
+        assert line[key] == a.module.summary_of(stats), a.stem

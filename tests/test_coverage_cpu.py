@@ -6,7 +6,7 @@ import json
 import numpy as np
 import pytest
 
-from coarsegrainingvae_amd import _lib, backmap as bm, coverage, run_ala
+from coarsegrainingvae_amd import _lib, backmap as bm, coverage, ensemble, run_ala
 import superpose_restatement as R
 
 
@@ -127,7 +127,8 @@ def test_host_wrappers_refuse_bad_selections_without_a_launch():
             call(a[0], b)
     with pytest.raises(ValueError, match="dense matrix is limited"):
         coverage.rmsd_matrix(np.zeros((4097, 1, 3), np.float32), np.zeros((4096, 1, 3), np.float32))
-    assert coverage._check_sel(None, 6).tolist() == list(range(6)) and coverage._check_sel([5, 0], 6).dtype == np.int32
+    as_coverage = dict(purpose="superpose", unique=False, max_atoms=coverage.limits()["atoms"])
+    assert ensemble.selection(None, 6, **as_coverage).tolist() == list(range(6)) and ensemble.selection([5, 0], 6, **as_coverage).dtype == np.int32
     with pytest.raises(ValueError, match="two reference frames"):
         coverage.compare(a[:1], b, np.full(6, 6))
 

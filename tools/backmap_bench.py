@@ -93,7 +93,7 @@ def main():
         gen = torch.from_numpy(out["xyz"]).to(DEV)
         plan = ev.QualityPlan(np.tile(z, n_frames), np.arange(n_frames + 1) * len(z), DEV, radii=FILL)
         blist = ev.BondList(bonds, plan)
-        check = lambda: ev._read_back(list(ev.ensemble_check(gen.reshape(-1, 3), K, plan, blist)))
+        check = lambda: ev.read_back(list(ev.ensemble_check(gen.reshape(-1, 3), K, plan, blist)))
         if args.only_check:
             for _ in range(20):
                 check()
