@@ -229,6 +229,12 @@ PROTOTYPES = {
     "cgv_contact_workspace_bytes": (_sz, [_i, _i]),
     "cgv_contact_counts": (_i, [_p] * 4 + [_i, _i, _i, _f] + [_p] * 5 + [_p, _sz, _p]),
     "cgv_contact_group_counts": (_i, [_p] * 5 + [_i, _i, _i, _i, _f] + [_p] * 5 + [_p, _sz, _p]),
+    "cgv_sasa_max_atoms": (_i, []),
+    "cgv_sasa_max_points": (_i, []),
+    "cgv_sasa_max_classes": (_i, []),
+    "cgv_sasa_max_structures": (_i, []),
+    "cgv_sasa_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_sasa_counts": (_i, [_p] * 5 + [_i] * 5 + [_p] * 5 + [_p, _sz, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

@@ -27,13 +27,16 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # path from coordinates to bin index is restated on the host operation for operation; the TICA kernels' fp32 distances
 # are restated in numpy.float32 bit for bit; the two forms of the betweenness kernel and of the baseline trainer must
 # round alike; the contact kernels test sq_dist2 against a cutoff that the host restates bit for bit; the alignment
-# kernel's rotation solve (csrc/superpose_rot.h) is the text a host program compiles to measure it against LAPACK.
+# kernel's rotation solve (csrc/superpose_rot.h) is the text a host program compiles to measure it against LAPACK; the
+# surface kernel builds a sphere point as a rounded product plus a rounded sum and tests sq_dist2 against a rounded r * r,
+# all restated on the host bit for bit.
 # kde.hip has NO entry: its fp32 stage sums are checked against an error bound, not restated bit for bit, and its one
 # contraction that matters (the minimum image) is written as an explicit fmaf -- the default flags do
 SOURCE_FLAGS = {"newman.hip": ["-ffp-contract=off"], "baseline.hip": ["-ffp-contract=off"],
                 "sample_quality.hip": ["-ffp-contract=off"], "ensemble_check.hip": ["-ffp-contract=off"],
                 "internal_hist.hip": ["-ffp-contract=off"], "tica.hip": ["-ffp-contract=off"],
-                "contact_map.hip": ["-ffp-contract=off"], "align_mean.hip": ["-ffp-contract=off"]}
+                "contact_map.hip": ["-ffp-contract=off"], "align_mean.hip": ["-ffp-contract=off"],
+                "sasa.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -1298,6 +1298,55 @@ int cgv_kde_sums(const float* samples, const float* points, const float* period 
                  int n_points, int d, int splits, double* sums, int32_t* n_skipped, void* workspace, size_t workspace_bytes,
                  void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K23  solvent-accessible surface area of an ensemble (Shrake-Rupley) -- which atoms a structure turns to the solvent:
+ * for every structure and every selected atom, how many of n_points points on the atom's probe-inflated sphere lie inside
+ * no other selected atom's inflated sphere.  Nothing in the reference computes it.  Lengths in Angstrom.
+ *   xyz [n_structures,n_atoms,3] fp32
+ *   sel [m] int32, 1 <= m <= n_atoms          the molecule: the atoms probed and the only occluders, in any order; all
+ *                                             indices below are positions in sel.  An index outside [0, n_atoms) reads
+ *                                             atom 0 (the host wrapper refuses such a selection); nothing is read out of
+ *                                             bounds.
+ *   r [m] fp32                                the inflated radius of a selected atom, fp32(fp32(R) + fp32(probe)): the
+ *                                             CALLER's sum.  r2_j = r_j * r_j, one rounded fp32 product.
+ *   u [n_points,3] fp32                       points of the unit sphere, the CALLER's (golden spiral, built in fp64 and
+ *                                             rounded once)
+ *   cls [m] int32 in [0, n_classes)           the class of a selected atom (a value outside counts as class 0)
+ * Point k of atom i is c_i + r_i * u_k per component, the product rounded, then the sum (no fma).  It is buried iff some
+ * position j != i of sel has (dx*dx + dy*dy) + dz*dz < r2_j for its difference to c_j, fp32 with every operation
+ * individually rounded (csrc/sq_dist.h: sq_dist2) and strict <; j != i is by position, not by coordinates.  count[s,i] is
+ * the number of points of atom i that are not buried, 0 .. n_points: a host that restates the arithmetic gets every integer
+ * below exactly, and the area of an atom is the host's 4 pi r_i^2 count / n_points -- no floating-point result leaves the
+ * device.
+ *   counts [n_structures,m] int32 or NULL     overwritten: count[s,i]
+ *   class_counts [n_structures,n_classes] int32   overwritten: the sum of count[s,i] over the atoms of a class
+ *   atom_sum, atom_sumsq [m] int64            count and count^2 of this call's good structures are ADDED: a caller cuts a
+ *                                             long ensemble into launches and zeroes them once
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate inside sel.  Its
+ *                                             rows of counts and class_counts are -1 and it enters no sum.
+ * Launches: one wave per structure gathers sel into a packed copy [n_structures, m] float4 (x, y, z, r2) in the workspace
+ *   and writes bad and a flag per structure; then grid (structures x atom ranges, at most 1024 blocks that loop) x 256
+ *   threads: a block stages a structure's packed atoms and the sphere points in LDS, a wave owns atoms in turn, compacts the
+ *   occluders that pass a pre-filter on |c_i - c_j| into a list in LDS (capacity m - 1), its lanes own points and walk the
+ *   list until every live point of the wave is buried.  The pre-filter is a proven superset of the atoms that can bury a
+ *   point for |coordinates| <= 4096 (derivation: csrc/sasa.hip); a structure beyond that takes every j != i and is not bad.
+ *   The atoms of a structure are split over several blocks when the structures alone would leave CUs idle.  Integer sums
+ *   meet in atomicAdd, whose order does not matter: the same bits on every call, however the structures are cut.
+ * workspace: cgv_sasa_workspace_bytes(n_structures, m, n_points) bytes (0 beyond a limit), 16-byte aligned, contents need
+ *   not survive.
+ * Limits: m <= cgv_sasa_max_atoms() (4096: a structure's atoms, its lists and sums live in the 160 KB of LDS of a CU),
+ *   n_points <= cgv_sasa_max_points(), n_classes <= cgv_sasa_max_classes(), n_structures <= cgv_sasa_max_structures() per
+ *   launch; beyond a limit the call fails (CGV_E_BADARG) before any launch.  Bound: see DESIGN.md (K23 row). */
+int cgv_sasa_max_atoms(void);
+int cgv_sasa_max_points(void);
+int cgv_sasa_max_classes(void);
+int cgv_sasa_max_structures(void);
+size_t cgv_sasa_workspace_bytes(int n_structures, int m, int n_points);
+int cgv_sasa_counts(const float* xyz, const int32_t* sel /*[m]*/, const float* r /*[m]*/, const float* u /*[n_points,3]*/,
+                    const int32_t* cls /*[m]*/, int n_structures, int n_atoms, int m, int n_points, int n_classes,
+                    int32_t* counts /*[S,m] or NULL*/, int32_t* class_counts /*[S,n_classes]*/, int64_t* atom_sum /*[m]*/,
+                    int64_t* atom_sumsq /*[m]*/, int32_t* bad /*[S]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
