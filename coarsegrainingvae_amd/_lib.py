@@ -235,6 +235,10 @@ PROTOTYPES = {
     "cgv_sasa_max_structures": (_i, []),
     "cgv_sasa_workspace_bytes": (_sz, [_i, _i, _i]),
     "cgv_sasa_counts": (_i, [_p] * 5 + [_i] * 5 + [_p] * 5 + [_p, _sz, _p]),
+    "cgv_cluster_max_structures": (_i, []),
+    "cgv_cluster_workspace_bytes": (_sz, [_i, _i]),
+    "cgv_cluster_pack": (_i, [_p, _i, _i, _i, _i, _i, C.c_double, _p, _p]),
+    "cgv_cluster_gromos": (_i, [_p, _p, _i, _p, _p, _p, _p, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

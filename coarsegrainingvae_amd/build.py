@@ -31,7 +31,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # surface kernel builds a sphere point as a rounded product plus a rounded sum and tests sq_dist2 against a rounded r * r,
 # all restated on the host bit for bit.
 # kde.hip has NO entry: its fp32 stage sums are checked against an error bound, not restated bit for bit, and its one
-# contraction that matters (the minimum image) is written as an explicit fmaf -- the default flags do
+# contraction that matters (the minimum image) is written as an explicit fmaf -- the default flags do; cluster.hip has none
+# either: its only floating-point operation is a comparison of doubles that K17 wrote
 SOURCE_FLAGS = {"newman.hip": ["-ffp-contract=off"], "baseline.hip": ["-ffp-contract=off"],
                 "sample_quality.hip": ["-ffp-contract=off"], "ensemble_check.hip": ["-ffp-contract=off"],
                 "internal_hist.hip": ["-ffp-contract=off"], "tica.hip": ["-ffp-contract=off"],

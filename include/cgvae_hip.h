@@ -1347,6 +1347,55 @@ int cgv_sasa_counts(const float* xyz, const int32_t* sel /*[m]*/, const float* r
                     int32_t* counts /*[S,m] or NULL*/, int32_t* class_counts /*[S,n_classes]*/, int64_t* atom_sum /*[m]*/,
                     int64_t* atom_sumsq /*[m]*/, int32_t* bad /*[S]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K24  clustering of an ensemble by superposed RMSD (Daura et al., "GROMOS": the default of `gmx cluster -method gromos`)
+ * -- which conformational states the data has: the dense squared RMSDs of K17 become a bit-packed neighbour matrix, and
+ * the greedy loop (the structure with most neighbours becomes a centre, it and its neighbours leave, repeat) runs on the
+ * device, so no [S,S] fp64 tensor reaches the host.  Nothing in the reference computes it.
+ *   c2 = double(cutoff) * double(cutoff), the CALLER's product.  All comparisons are exact.
+ *   For structures p < q: adj(p, q) = adj(q, p) = (d2(p, q) <= c2), d2(p, q) the value cgv_superpose writes to `dense` for
+ *   row p, column q of the set against itself.  Only the UPPER triangle decides (the transposed pair may differ in its last
+ *   bits; the graph must be symmetric).  adj(p, p) = 1 iff p is good: dense[p, p] is not NaN.  NaN compares false: a bad
+ *   structure has an empty row and an empty column.
+ *   bits [S, W] uint64, W = ceil(S / 64): bit (q & 63) of word q >> 6 of row p is adj(p, q); bits at columns >= S are 0.
+ *
+ * cgv_cluster_pack: one dense rectangle of a pair of chunks of the set.
+ *   dense [sa,sb] fp64                        cgv_superpose's `dense` for rows off_a .. off_a + sa, columns off_b .. off_b + sb
+ *   off_a <= off_b, both multiples of 64; the chunks are the same one (off_a == off_b, sa == sb) or apart (off_a + sa <=
+ *   off_b); only the chunk that ends at n_structures may be no multiple of 64 long.
+ *   It writes every word of `bits` the rectangle decides: rows off_a.., words off_b / 64.. (in the diagonal chunk: from
+ *   dense[min(i, j), max(i, j)]), and, mirrored, rows off_b.., words off_a / 64...  A caller that passes every pair of
+ *   chunks with off_a <= off_b once has written every word exactly once; the result does not depend on the chunk size.
+ *   Launch: grid (column tiles, row tiles) x 256 threads, a 64 x 64 tile per block: a wave reads 64 consecutive doubles of
+ *   a row, ballots the comparison, one lane stores the word and keeps it in LDS; the mirrored words are ballots over the 64
+ *   staged words, so every read of `dense` is coalesced.  No atomics.
+ * cgv_cluster_gromos: the clustering of a finished bit matrix.
+ *   good [W] uint64 or NULL                   the structures that take part (a bit mask); NULL: those with their diagonal
+ *                                             bit.  Bits at positions >= n_structures are ignored.
+ *   alive starts as the good structures, count[i] = popcount(row_i & alive).  An iteration k: the centre c is the alive
+ *   structure of largest count, lowest index on ties; its members are row_c & alive plus c itself, whatever its diagonal
+ *   bit says; they get label k and leave alive; for every removed r the counts of its alive neighbours are decremented
+ *   (the matrix is symmetric; no row is recounted).  At most n_structures iterations, each removes at least its centre: a
+ *   matrix that is not symmetric gives other clusters, never a hang.
+ *   label [S] int32                           overwritten: the cluster of a structure, -1 for one that is not good
+ *   centre [S], size [S] int32                overwritten: the first *n_clusters entries are the centre and the number of
+ *                                             members of a cluster, in the order found; the rest is -1 / 0
+ *   n_clusters [1] int32                      overwritten
+ *   Launch: ONE workgroup of 1024 threads with alive, the members of the iteration, the counts and the reduction scratch in
+ *   LDS (dynamic, 272 bytes per 64 structures + 144); decrements are integer LDS atomics.  Integers only: the same bits
+ *   on every call.
+ * cgv_cluster_workspace_bytes(n_structures, chunk): the bit matrix (128 MiB at the limit) followed by one dense chunk of
+ *   `chunk` rounded up to 64, squared, doubles; 0 beyond a limit.
+ * Limits: n_structures <= cgv_cluster_max_structures() (32768: what the 160 KB of LDS of a CU hold); beyond it the calls
+ *   fail (CGV_E_BADARG) before any launch.  See DESIGN.md (K24 row). */
+int cgv_cluster_max_structures(void);
+size_t cgv_cluster_workspace_bytes(int n_structures, int chunk);
+int cgv_cluster_pack(const double* dense /*[sa,sb]*/, int sa, int sb, int off_a, int off_b, int n_structures, double c2,
+                     uint64_t* bits /*[S,W]*/, void* stream);
+int cgv_cluster_gromos(const uint64_t* bits /*[S,W]*/, const uint64_t* good /*[W] or NULL*/, int n_structures,
+                       int32_t* label /*[S]*/, int32_t* centre /*[S]*/, int32_t* size /*[S]*/, int32_t* n_clusters /*[1]*/,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
