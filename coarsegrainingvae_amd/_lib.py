@@ -239,6 +239,13 @@ PROTOTYPES = {
     "cgv_cluster_workspace_bytes": (_sz, [_i, _i]),
     "cgv_cluster_pack": (_i, [_p, _i, _i, _i, _i, _i, C.c_double, _p, _p]),
     "cgv_cluster_gromos": (_i, [_p, _p, _i, _p, _p, _p, _p, _p]),
+    "cgv_hbond_max_structures": (_i, []),
+    "cgv_hbond_max_hydrogens": (_i, []),
+    "cgv_hbond_max_acceptors": (_i, []),
+    "cgv_hbond_row_tile": (_i, []),
+    "cgv_hbond_chunk": (_i, []),
+    "cgv_hbond_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_hbond_counts": (_i, [_p] * 6 + [_i, _i, _i, _i, _f, _f] + [_p] * 5 + [_p, _sz, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

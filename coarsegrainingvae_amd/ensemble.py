@@ -1,5 +1,5 @@
 """What the analyses of ensembles share (``evaluate``, ``distributions``, ``tica``, ``coverage``, ``contacts``,
-``flexibility``, ``density``, ``sasa``, ``cluster``): the host plumbing around their kernels and the topology helpers more
+``flexibility``, ``density``, ``sasa``, ``cluster``, ``hbonds``): the host plumbing around their kernels and the topology helpers more
 than one of them reads.  This module imports none of them, so each imports it at module level; what is here is public, and nothing here
 launches a kernel.
 """

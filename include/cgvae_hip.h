@@ -1396,6 +1396,56 @@ int cgv_cluster_gromos(const uint64_t* bits /*[S,W]*/, const uint64_t* good /*[W
                        int32_t* label /*[S]*/, int32_t* centre /*[S]*/, int32_t* size /*[S]*/, int32_t* n_clusters /*[1]*/,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K25  hydrogen bonds of an ensemble (Baker-Hubbard, intramolecular) -- which donor hydrogens point at which acceptors:
+ * how often every pair (donor hydrogen, acceptor) is bonded over the structures, per structure the number of bonds and of
+ * native bonds, and on request every bond of every structure as a bit.  Nothing in the reference computes it.  Lengths in
+ * Angstrom.
+ *   xyz [n_structures,n_atoms,3] fp32
+ *   don_h, don_d [n_hydrogens] int32          a donor hydrogen and the heavy atom it is bonded to: the CALLER's tables
+ *   acc [n_acceptors] int32                   the acceptors.  An index outside [0, n_atoms) reads atom 0 (the host wrapper
+ *                                             builds the tables itself); nothing is read out of bounds.
+ *   excluded [n_hydrogens,W] uint64, W = ceil(n_acceptors / 64): bit (a & 63) of word a >> 6 of row h: the pair (h, a) never
+ *                                             counts (A is D, A is bonded to D, or the caller says so).  Bits past
+ *                                             n_acceptors are ignored.
+ *   native [n_hydrogens,W] uint64 or NULL     the pairs n_native counts, in the same layout
+ * A pair that is not excluded is bonded in a structure iff, in fp32 with every operation individually rounded (no fma),
+ *   d2 = sq_dist2(A, H), l2 = sq_dist2(D, H)  ((dx*dx + dy*dy) + dz*dz, csrc/sq_dist.h),
+ *   dot = (ux*vx + uy*vy) + uz*vz with u = D - H and v = A - H, and
+ *   d2 < cutoff2  and  dot < 0  and  dot*dot > (c2 * l2) * d2.
+ * cutoff2 is the CALLER's fp32(cutoff) * fp32(cutoff), c2 the CALLER's fp32(cos(angle)^2) of the least D-H...A angle, which
+ * must lie in [90, 180) degrees for the test to mean cos(D-H-A) < cos(angle).  A host that restates the arithmetic gets
+ * every integer below exactly; no floating-point result leaves the device.
+ *   pair_counts [n_hydrogens,n_acceptors] int64   ADDED to: in how many good structures of this call the pair is bonded; a
+ *                                             caller cuts a long ensemble into launches and zeroes it once
+ *   n_hbonds [n_structures] int32             overwritten: the bonds of a structure
+ *   n_native [n_structures] int32             overwritten: those of them in `native` (0 when native is NULL)
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate in an atom of
+ *                                             don_h, don_d or acc.  Its n_hbonds and n_native are -1, it enters no sum.
+ *   bits [n_structures,n_hydrogens,W] uint64 or NULL   overwritten: bit (a & 63) of word a >> 6 is set iff (h, a) is bonded;
+ *                                             bits past n_acceptors are 0, the rows of a bad structure are 0
+ * Launches: one wave per structure gathers the table atoms into a packed copy [n_structures, 2 n_hydrogens + n_acceptors]
+ *   float4 in the workspace (NaN for a bad structure) and writes bad; then grid (W, row tiles of cgv_hbond_row_tile()
+ *   hydrogens, slices of the structure axis) x 256 threads: a lane owns an acceptor, a wave 8 rows whose counters its lanes
+ *   keep in registers; cgv_hbond_chunk() structures at a time go through LDS; the wave's ballot of the test is the word of
+ *   `bits`.  Integer sums meet in atomicAdd: the same bits on every call, however the structures are cut.
+ * workspace: cgv_hbond_workspace_bytes(n_structures, n_hydrogens, n_acceptors) bytes (0 beyond a limit), 16-byte aligned,
+ *   contents need not survive.
+ * Limits: 1 <= n_hydrogens <= cgv_hbond_max_hydrogens(), 1 <= n_acceptors <= cgv_hbond_max_acceptors(), n_structures <=
+ *   cgv_hbond_max_structures() per launch; beyond a limit, and for a cutoff2 or c2 that is no number of its range, the call
+ *   fails (CGV_E_BADARG) with its reason before any launch.  See DESIGN.md (HB row). */
+int cgv_hbond_max_structures(void);
+int cgv_hbond_max_hydrogens(void);
+int cgv_hbond_max_acceptors(void);
+int cgv_hbond_row_tile(void);
+int cgv_hbond_chunk(void);
+size_t cgv_hbond_workspace_bytes(int n_structures, int n_hydrogens, int n_acceptors);
+int cgv_hbond_counts(const float* xyz, const int32_t* don_h /*[nH]*/, const int32_t* don_d /*[nH]*/, const int32_t* acc /*[nA]*/,
+                     const uint64_t* excluded /*[nH,W]*/, const uint64_t* native /*[nH,W] or NULL*/, int n_structures,
+                     int n_atoms, int n_hydrogens, int n_acceptors, float cutoff2, float c2, int64_t* pair_counts /*[nH,nA]*/,
+                     int32_t* n_hbonds /*[S]*/, int32_t* n_native /*[S]*/, int32_t* bad /*[S]*/,
+                     uint64_t* bits /*[S,nH,W] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
