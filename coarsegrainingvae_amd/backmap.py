@@ -88,6 +88,7 @@ import torch
 from . import contacts, coverage, density, distributions, flexibility, tica
 from . import evaluate as ev
 from .analyses import ANALYSES, BY_STEM
+from .compare_cli import read_npz
 from .train import build_model
 
 
@@ -393,16 +394,6 @@ def kde_bandwidth(text: str):
     return value
 
 
-def _npz(path: str, need) -> dict:
-    if not os.path.exists(path):
-        raise SystemExit(f"{path}: no such file")
-    with np.load(path, allow_pickle=False) as f:
-        missing = sorted(set(need) - set(f.files))
-        if missing:
-            raise SystemExit(f"{path}: missing {missing}")
-        return {k: f[k] for k in f.files}
-
-
 def read_inputs(args, params, device=None) -> dict:
     """The CLI's input files as ``cg_xyz``, ``z``, ``bonds`` (``None`` where absent), checked against the run's mapping.
     ``-traj`` frames are coarse-grained on ``device`` (``ops.scatter_mean`` over the mapping, no rotation)."""
@@ -422,9 +413,9 @@ def read_inputs(args, params, device=None) -> dict:
     if getattr(args, "ref", None) and not need_ref:
         raise SystemExit("-ref is the reference of " + " / ".join(f"--{a.stem}_stats" for a in ANALYSES))
     if args.cg:
-        cg = np.asarray(_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
+        cg = np.asarray(read_npz(args.cg, ["cg_xyz"])["cg_xyz"], dtype=np.float32)
     else:
-        f = _npz(args.traj, ["xyz", "z", "bonds"])
+        f = read_npz(args.traj, ["xyz", "z", "bonds"])
         xyz, z, bonds, starts = np.asarray(f["xyz"], dtype=np.float32), f["z"], f["bonds"], f.get("traj_starts")
         if xyz.ndim != 3 or xyz.shape[1:] != (n, 3):
             raise SystemExit(f"{args.traj}: xyz is {xyz.shape}, the run's mapping has {n} atoms")
@@ -435,7 +426,7 @@ def read_inputs(args, params, device=None) -> dict:
         cg = scatter_mean(torch.from_numpy(xyz).to(device).reshape(T * n, 3).contiguous(), index, dim=0,
                           dim_size=T * N).reshape(T, N, 3).cpu().numpy()
     if args.top:
-        f = _npz(args.top, ["z", "bonds"])
+        f = read_npz(args.top, ["z", "bonds"])
         z, bonds = f["z"], f["bonds"]
     if cg.ndim != 3 or cg.shape[1:] != (N, 3):
         raise SystemExit(f"cg_xyz is {cg.shape}, the run's mapping has {N} beads")
@@ -452,7 +443,7 @@ def read_inputs(args, params, device=None) -> dict:
         if bonds is None:
             raise SystemExit(f"{switch} needs a topology (-top, or the z / bonds of -traj)")
         if args.ref:
-            f = _npz(args.ref, ["xyz", "z"])
+            f = read_npz(args.ref, ["xyz", "z"])
             ref_xyz, starts = np.asarray(f["xyz"], dtype=np.float32), f.get("traj_starts")
             if ref_xyz.ndim != 3 or ref_xyz.shape[1:] != (n, 3):
                 raise SystemExit(f"{args.ref}: xyz is {ref_xyz.shape}, the topology has {n} atoms")

@@ -27,16 +27,14 @@ statistics of ``compare`` go to ``-out``, the states of all structures to ``-lab
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import os
 import sys
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import _lib, coverage, ensemble
+from . import _lib, compare_cli, coverage, ensemble
 from .ensemble import check_sets, device_of, read_back, select_atoms, structures
 
 MAX_CHUNK = 8192                       # structures_per_launch is capped here: one dense chunk is then at most 512 MiB
@@ -307,28 +305,14 @@ def summary_of(stats: dict) -> dict:
 
 # ----------------------------------------------------------------------------- command line
 def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m coarsegrainingvae_amd.cluster",
-                                description="conformational states of a reference by RMSD clustering, and how generated structures populate them")
-    p.add_argument("-gen", required=True, help="npz with xyz [T,K,n,3] or [S,n,3]: the generated structures (backmap -out)")
-    p.add_argument("-ref", required=True, help="npz with xyz [T,n,3]: the reference frames, at least two")
-    p.add_argument("-top", default=None, help="npz with z; default: that of -ref")
+    p = compare_cli.base_parser("python -m coarsegrainingvae_amd.cluster",
+                                "conformational states of a reference by RMSD clustering, and how generated structures populate them",
+                                top_help="npz with z; default: that of -ref")
     p.add_argument("-cluster_cutoff", type=float, default=1.0, help="neighbour criterion: superposed RMSD in Angstrom (1.0)")
     p.add_argument("-cluster_atoms", choices=("heavy", "all"), default="heavy", help="the atoms superposed and compared (heavy)")
     p.add_argument("-cluster_stride", type=int, default=1, help="cluster every k-th reference frame (1)")
     p.add_argument("-labels", default=None, help="npz for the centres and the state of every frame and structure (not written)")
-    p.add_argument("-out", default="cluster_stats.json", help="where the full statistics go (cluster_stats.json)")
-    p.add_argument("-device", default="cuda")
-    return p
-
-
-def _npz(path: str, need) -> dict:
-    if not os.path.exists(path):
-        raise SystemExit(f"{path}: no such file")
-    with np.load(path, allow_pickle=False) as f:
-        missing = sorted(set(need) - set(f.files))
-        if missing:
-            raise SystemExit(f"{path}: missing {missing}")
-        return {k: f[k] for k in f.files}
+    return compare_cli.finish_parser(p, "cluster_stats.json")
 
 
 def read_inputs(args) -> dict:
@@ -338,20 +322,7 @@ def read_inputs(args) -> dict:
         raise SystemExit("-cluster_cutoff must be a finite length >= 0 in Angstrom")
     if args.cluster_stride < 1:
         raise SystemExit("-cluster_stride must be at least 1")
-    ref = _npz(args.ref, ["xyz"])
-    top = _npz(args.top, ["z"]) if args.top else ref
-    if "z" not in top:
-        raise SystemExit(f"{args.ref}: missing z (or pass -top)")
-    z = np.asarray(top["z"]).astype(np.int64).reshape(-1)
-    n = z.shape[0]
-    ref_xyz = np.asarray(ref["xyz"], dtype=np.float32)
-    if ref_xyz.ndim != 3 or ref_xyz.shape[1:] != (n, 3):
-        raise SystemExit(f"{args.ref}: xyz is {ref_xyz.shape}, the topology has {n} atoms")
-    if ref_xyz.shape[0] < 2:
-        raise SystemExit(f"{args.ref}: at least two reference frames are needed")
-    gen_xyz = np.asarray(_npz(args.gen, ["xyz"])["xyz"], dtype=np.float32)
-    if gen_xyz.ndim not in (3, 4) or gen_xyz.shape[-2:] != (n, 3):
-        raise SystemExit(f"{args.gen}: xyz is {gen_xyz.shape}, the topology has {n} atoms")
+    ref_xyz, gen_xyz, z, _, _ = compare_cli.read_sets(args, need=("z",))
     if select_atoms(z, args.cluster_atoms).shape[0] == 0:
         raise SystemExit(f"the topology has no {args.cluster_atoms} atoms")
     lim = limits()["structures"]
@@ -359,22 +330,19 @@ def read_inputs(args) -> dict:
     if used > lim:
         raise SystemExit(f"{used} reference frames to cluster, the kernel holds {lim}: pass -cluster_stride "
                          f"{-(-ref_xyz.shape[0] // lim)} or more")
-    return {"ref_xyz": ref_xyz, "gen_xyz": gen_xyz.reshape(-1, n, 3), "z": z}
+    return {"ref_xyz": ref_xyz, "gen_xyz": gen_xyz, "z": z}
 
 
 def main(argv=None) -> dict:
     args = parser().parse_args(argv)
     inp = read_inputs(args)
-    try:
+    with compare_cli.refusing():
         stats, labels = _run(inp["ref_xyz"], inp["gen_xyz"], inp["z"], args.cluster_cutoff, args.cluster_atoms,
                              args.cluster_stride, 0.01, 4096, args.device)
-    except ValueError as err:
-        raise SystemExit(str(err))
-    with open(args.out, "w") as f:
-        json.dump(stats, f)
+    compare_cli.write_stats(stats, args.out)
     if args.labels:
         np.savez(args.labels, **labels)
-    print(json.dumps({"cluster_stats": summary_of(stats), "out": args.out}), flush=True)
+    compare_cli.print_summary("cluster", summary_of(stats), args.out)
     return stats
 
 

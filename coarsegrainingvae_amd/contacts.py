@@ -29,7 +29,6 @@ from . import _lib, ensemble
 from .ensemble import adjacency, check_sets, device_of, groups_of, read_back, scalar_block, select_atoms, structures
 
 MAX_GROUPS = 4096                      # include/cgvae_hip.h: the group kernel's grid
-WORKSPACE_BYTES = 1 << 28              # structures_per_launch is lowered until the packed copy of a launch fits this
 
 
 def limits() -> Dict[str, int]:
@@ -132,7 +131,7 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
     P = m if groups is None else int(ids.shape[0])
     nat = None if native is None else _square(native, P, "native")
     dev = device_of(x, device)
-    M = max(1, min(int(structures_per_launch), lim["structures"], max(64, WORKSPACE_BYTES // (16 * m))))
+    M = ensemble.structures_per_launch(structures_per_launch, lim["structures"], 16 * m)
     total = torch.zeros(P, P, dtype=torch.int64, device=dev)
     part = torch.zeros(P, P, dtype=torch.int32, device=dev)
     per = {"n_contacts": torch.zeros(S, dtype=torch.int32, device=dev), "n_native": torch.zeros(S, dtype=torch.int32, device=dev),
@@ -145,8 +144,7 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
         d_gs = None if gstart is None else torch.from_numpy(gstart).to(dev)
         need = int(lib.cgv_contact_workspace_bytes(min(M, S), m))
         ws = torch.empty((need + 15) // 16 * 4, dtype=torch.float32, device=dev)
-        for start in range(0, S, M):
-            chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+        for start, chunk in ensemble.chunks(x, M, dev):
             k = int(chunk.shape[0])
             if start:
                 part.zero_()
@@ -232,10 +230,7 @@ def compare_from_counts(even: dict, odd: dict, gen: dict, allowed, native, label
         if n_native > 0:
             q = [good(r, "n_native").astype(np.float64) / n_native for r in (even, odd, gen)]
             q_block = scalar_block(q[0], q[1], q[2], 0.0, 1.0, n_bins)
-    n_of = lambda *rs: int(sum(np.asarray(r["bad"]).shape[0] for r in rs))
-    n_bad = lambda *rs: int(sum(np.asarray(r["bad"], dtype=bool).sum() for r in rs))
-    return {"n_ref": n_of(even, odd), "n_gen": n_of(gen), "n_bad_ref": n_bad(even, odd), "n_bad_gen": n_bad(gen),
-            "params": dict(params or {}, n_bins=int(n_bins)), "labels": labels,
+    return {**ensemble.set_sizes(even, odd, gen), "params": dict(params or {}, n_bins=int(n_bins)), "labels": labels,
             "p_ref": None if p_ref is None else p_ref.tolist(), "p_gen": None if p_gen is None else p_gen.tolist(),
             "map_rmse": rmse, "map_max_dev": max_dev,
             "floor": {"map_rmse": f_rmse, "map_max_dev": f_max, "q_jsd": q_block["floor"] if q_block else None,
@@ -291,12 +286,11 @@ def compare(ref_xyz, gen_xyz, z, bonds, atoms="heavy", cutoff: float = 4.5, excl
 
 CONTACT_STATS_KEYS = ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "params", "labels", "p_ref", "p_gen", "map_rmse", "map_max_dev",
                       "floor", "top_pairs", "n_native", "q", "rg")
-_MOMENTS = ("jsd", "mean_ref", "std_ref", "mean_gen", "std_gen")
 
 
 def summary_of(stats: dict) -> dict:
     """What the command-line tools put under ``"contact_stats"`` in their JSON summary line: no maps, no histograms."""
     short = {k: stats[k] for k in ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "map_rmse", "map_max_dev", "floor", "n_native")}
     for k in ("q", "rg"):
-        short[k] = None if stats[k] is None else {name: stats[k][name] for name in _MOMENTS}
+        short[k] = ensemble.short_block(stats[k])
     return short

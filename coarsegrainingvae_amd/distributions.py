@@ -172,8 +172,7 @@ def histograms(xyz, coords: InternalCoords, n_bins: int = 36, n_bins2: int = 36,
     shape, shape2 = (coords.n_features, n_bins + 3), (coords.n_pairs, n_bins2, n_bins2)
     total, total2 = torch.zeros(shape, dtype=torch.int64, device=dev), torch.zeros(shape2, dtype=torch.int64, device=dev)
     part, part2 = torch.zeros(shape, dtype=torch.int32, device=dev), torch.zeros(shape2, dtype=torch.int32, device=dev)
-    for start in range(0, int(x.shape[0]), M):
-        chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+    for start, chunk in ensemble.chunks(x, M, dev):
         if start:
             part.zero_(), part2.zero_()
         internal_hist(chunk, table, n_bins, n_bins2, bond_range, part, part2)
@@ -224,8 +223,7 @@ def feature_values(xyz, coords: InternalCoords, rows=None, structures_per_launch
     table = _DeviceTable(sub, dev)
     values = torch.empty((int(x.shape[0]), sub.n_features), dtype=torch.float64, device=dev)
     n_invalid = torch.zeros(1, dtype=torch.int32, device=dev)
-    for start in range(0, int(x.shape[0]), M):
-        chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+    for start, chunk in ensemble.chunks(x, M, dev):
         internal_values(chunk, table, values[start:start + M], n_invalid)
     out, bad = read_back([values, n_invalid])
     return (out, int(bad[0])) if return_invalid else out

@@ -1,16 +1,19 @@
 """What the analyses of ensembles share (``evaluate``, ``distributions``, ``tica``, ``coverage``, ``contacts``,
 ``flexibility``, ``density``, ``sasa``, ``cluster``, ``hbonds``): the host plumbing around their kernels and the topology helpers more
 than one of them reads.  This module imports none of them, so each imports it at module level; what is here is public, and nothing here
-launches a kernel.
+launches a kernel.  The front end of the stand-alone command lines (``sasa``, ``cluster``, ``hbonds``: files, parser, summary line) is
+``compare_cli``, which imports this module and is imported by them.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+
+WORKSPACE_BYTES = 1 << 28              # structures_per_launch is lowered until the packed copy of a launch fits this
 
 
 # ----------------------------------------------------------------------------- device plumbing
@@ -48,6 +51,18 @@ def limits(prefix: str, keys=("structures", "atoms")) -> Dict[str, int]:
 def workspace(nbytes: int, device) -> torch.Tensor:
     """Scratch of at least ``nbytes`` bytes, in whole doubles (the kernels keep fp64 partial sums in it)."""
     return torch.empty((int(nbytes) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def structures_per_launch(requested: int, limit: int, bytes_per_structure: int) -> int:
+    """The request lowered to what a launch holds and to what keeps its packed copy within ``WORKSPACE_BYTES`` (never
+    below 64 for the budget's sake); at least 1."""
+    return max(1, min(int(requested), limit, max(64, WORKSPACE_BYTES // bytes_per_structure)))
+
+
+def chunks(x: torch.Tensor, M: int, dev) -> Iterator[Tuple[int, torch.Tensor]]:
+    """``(start, chunk)`` for every ``M`` structures of ``x``, the chunk on ``dev``, fp32 and contiguous."""
+    for start in range(0, int(x.shape[0]), M):
+        yield start, x[start:start + M].detach().to(dev, torch.float32).contiguous()
 
 
 # ----------------------------------------------------------------------------- selections and sets
@@ -221,3 +236,19 @@ def scalar_block(ref_e, ref_o, gen, lo, hi, n_bins) -> dict:
     (mr, sr), (mg, sg) = moments(ref), moments(gen)
     return {"range": [float(lo), float(hi)], "hist_ref": hr, "hist_gen": hg, "jsd": js_divergence(hr["counts"], hg["counts"]),
             "floor": js_divergence(he["counts"], ho["counts"]), "mean_ref": mr, "std_ref": sr, "mean_gen": mg, "std_gen": sg}
+
+
+MOMENTS = ("jsd", "mean_ref", "std_ref", "mean_gen", "std_gen")
+
+
+def short_block(block: Optional[dict], names=MOMENTS) -> Optional[dict]:
+    """What a ``summary_of`` keeps of a ``scalar_block``: no histograms."""
+    return None if block is None else {name: block[name] for name in names}
+
+
+def set_sizes(even: dict, odd: dict, gen: dict) -> Dict[str, int]:
+    """The structures of the reference (its even and odd frames) and of the generated set, and those left out as bad,
+    from the ``bad [S]`` of three results."""
+    n_of = lambda *rs: int(sum(np.asarray(r["bad"]).shape[0] for r in rs))
+    n_bad = lambda *rs: int(sum(np.asarray(r["bad"], dtype=bool).sum() for r in rs))
+    return {"n_ref": n_of(even, odd), "n_gen": n_of(gen), "n_bad_ref": n_bad(even, odd), "n_bad_gen": n_bad(gen)}

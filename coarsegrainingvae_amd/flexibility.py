@@ -311,13 +311,11 @@ def compare_from_runs(runs: dict, sel, group_labels=None, mean_rmsd=None, floor_
 
 FLEX_STATS_KEYS = ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "params", "labels", "rmsf_ref", "rmsf_gen", "pearson",
                    "profile_rmse", "ratio", "mean_rmsd", "rmsd_to_mean", "floor", "convergence", "top_atoms")
-_MOMENTS = ("jsd", "floor", "mean_ref", "std_ref", "mean_gen", "std_gen")
 
 
 def summary_of(stats: dict) -> dict:
     """What the command-line tools put under ``"flex_stats"`` in their JSON summary line: no profiles, no histograms."""
     short = {k: stats[k] for k in ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "pearson", "profile_rmse", "ratio", "mean_rmsd",
                                    "floor", "convergence")}
-    block = stats["rmsd_to_mean"]
-    short["rmsd_to_mean"] = None if block is None else {name: block[name] for name in _MOMENTS}
+    short["rmsd_to_mean"] = ensemble.short_block(stats["rmsd_to_mean"], ("jsd", "floor") + ensemble.MOMENTS[1:])
     return short

@@ -36,20 +36,16 @@ structure (``bits [S, nH, W]`` uint64 with the tables).
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import os
 import sys
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import _lib, ensemble
+from . import _lib, compare_cli, ensemble
 from .contacts import cutoff2_of
 from .ensemble import adjacency, check_sets, device_of, peptide_residues, read_back, scalar_block, structures
-
-WORKSPACE_BYTES = 1 << 28              # structures_per_launch is lowered until the packed copy of a launch fits this
 
 
 def limits() -> Dict[str, int]:
@@ -190,7 +186,7 @@ def hbond_counts(xyz, z, bonds, donor_elements=(7, 8), acceptor_elements=(7, 8),
     nat = None if native is None else _bool_mask(native, nH, nA, "native")
     W = (nA + 63) // 64
     dev = device_of(x, device)
-    M = max(1, min(int(structures_per_launch), lim["structures"], max(64, WORKSPACE_BYTES // (16 * (2 * nH + nA)))))
+    M = ensemble.structures_per_launch(structures_per_launch, lim["structures"], 16 * (2 * nH + nA))
     out = {"pair_counts": torch.zeros(nH, nA, dtype=torch.int64, device=dev), "n_hbonds": torch.zeros(S, dtype=torch.int32, device=dev),
            "n_native": torch.zeros(S, dtype=torch.int32, device=dev), "bad": torch.zeros(S, dtype=torch.int32, device=dev)}
     if per_pair:
@@ -202,8 +198,7 @@ def hbond_counts(xyz, z, bonds, donor_elements=(7, 8), acceptor_elements=(7, 8),
         d_nat = None if nat is None else _dev_words(pack_mask(nat), dev)
         need = int(lib.cgv_hbond_workspace_bytes(min(M, S), nH, nA))
         ws = torch.empty((need + 15) // 16 * 4, dtype=torch.float32, device=dev)
-        for start in range(0, S, M):
-            chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+        for start, chunk in ensemble.chunks(x, M, dev):
             k = int(chunk.shape[0])
             _lib.call("cgv_hbond_counts", _lib.ptr(chunk), _lib.ptr(d_h), _lib.ptr(d_d), _lib.ptr(d_a), _lib.ptr(d_excl),
                       _lib.ptr(d_nat), k, n, nH, nA, float(cutoff2), float(c2), _lib.ptr(out["pair_counts"]),
@@ -312,15 +307,12 @@ def compare_from_counts(even: dict, odd: dict, gen: dict, native=None, z=None, b
     if ne.size + no.size and ng.size:                          # one bin per integer, up to the most bonds either set has
         top = int(max(np.concatenate([ne, no]).max(), ng.max()))
         block = scalar_block(ne, no, ng, -0.5, top + 0.5, top + 1)
-    n_of = lambda *rs: int(sum(np.asarray(r["bad"]).shape[0] for r in rs))
-    n_bad = lambda *rs: int(sum(np.asarray(r["bad"], dtype=bool).sum() for r in rs))
     maps = {"backbone_ref": None, "backbone_gen": None}
     if z is not None and bonds is not None:
         for key, res in (("backbone_ref", ref), ("backbone_gen", gen)):
             m = backbone_map(res, z, bonds)
             maps[key] = None if m is None else m.tolist()
-    return {"n_ref": n_of(even, odd), "n_gen": n_of(gen), "n_bad_ref": n_bad(even, odd), "n_bad_gen": n_bad(gen),
-            "params": dict(params or {}), "n_donor_hydrogens": int(don_h.shape[0]), "n_acceptors": int(acc.shape[0]),
+    return {**ensemble.set_sizes(even, odd, gen), "params": dict(params or {}), "n_donor_hydrogens": int(don_h.shape[0]), "n_acceptors": int(acc.shape[0]),
             "pairs": pairs, "occupancy_rmse": rmse, "occupancy_pearson": pearson,
             "floor": {"occupancy_rmse": f_rmse, "occupancy_pearson": f_pearson, "n_hbonds_jsd": block["floor"] if block else None},
             "n_native": size, "native": [triple(h, a) for h, a in zip(*np.nonzero(nat))],
@@ -372,7 +364,6 @@ def compare(ref_xyz, gen_xyz, z, bonds, donor_elements=(7, 8), acceptor_elements
 HBOND_STATS_KEYS = ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "params", "n_donor_hydrogens", "n_acceptors", "pairs",
                     "occupancy_rmse", "occupancy_pearson", "floor", "n_native", "native", "kept_ref", "kept_gen", "missing",
                     "spurious", "n_hbonds", "backbone_ref", "backbone_gen")
-_MOMENTS = ("jsd", "mean_ref", "std_ref", "mean_gen", "std_gen")
 
 
 def summary_of(stats: dict) -> dict:
@@ -381,34 +372,19 @@ def summary_of(stats: dict) -> dict:
                                    "n_native", "kept_ref", "kept_gen")}
     short["n_missing"] = None if stats["missing"] is None else len(stats["missing"])
     short["n_spurious"] = None if stats["spurious"] is None else len(stats["spurious"])
-    short["n_hbonds"] = None if stats["n_hbonds"] is None else {name: stats["n_hbonds"][name] for name in _MOMENTS}
+    short["n_hbonds"] = ensemble.short_block(stats["n_hbonds"])
     return short
 
 
 # ----------------------------------------------------------------------------- command line
 def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m coarsegrainingvae_amd.hbonds",
-                                description="hydrogen bonds of generated structures against a reference")
-    p.add_argument("-gen", required=True, help="npz with xyz [T,K,n,3] or [S,n,3]: the generated structures (backmap -out)")
-    p.add_argument("-ref", required=True, help="npz with xyz [T,n,3]: the reference frames, at least two")
-    p.add_argument("-top", default=None, help="npz with z and bonds; default: those of -ref")
+    p = compare_cli.base_parser("python -m coarsegrainingvae_amd.hbonds", "hydrogen bonds of generated structures against a reference",
+                                top_help="npz with z and bonds; default: those of -ref")
     p.add_argument("-hbond_cutoff", type=float, default=2.5, help="largest H...A distance in Angstrom (2.5)")
     p.add_argument("-hbond_angle", type=float, default=120.0, help="least D-H...A angle in degrees, in [90, 180) (120)")
     p.add_argument("-hbond_native", type=float, default=0.5, help="reference occupancy from which a pair is native, in (0, 1] (0.5)")
     p.add_argument("-bits", default=None, help="npz that takes the bonds of every generated structure as bits (not written)")
-    p.add_argument("-out", default="hbond_stats.json", help="where the full statistics go (hbond_stats.json)")
-    p.add_argument("-device", default="cuda")
-    return p
-
-
-def _npz(path: str, need) -> dict:
-    if not os.path.exists(path):
-        raise SystemExit(f"{path}: no such file")
-    with np.load(path, allow_pickle=False) as f:
-        missing = sorted(set(need) - set(f.files))
-        if missing:
-            raise SystemExit(f"{path}: missing {missing}")
-        return {k: f[k] for k in f.files}
+    return compare_cli.finish_parser(p, "hbond_stats.json")
 
 
 def read_inputs(args) -> dict:
@@ -420,46 +396,27 @@ def read_inputs(args) -> dict:
         raise SystemExit("-hbond_angle must lie in [90, 180) degrees")
     if not (math.isfinite(args.hbond_native) and 0.0 < args.hbond_native <= 1.0):
         raise SystemExit("-hbond_native must lie in (0, 1]")
-    ref = _npz(args.ref, ["xyz"])
-    top = _npz(args.top, ["z", "bonds"]) if args.top else ref
-    if "z" not in top or "bonds" not in top:
-        raise SystemExit(f"{args.ref}: missing z / bonds (or pass -top)")
-    z = np.asarray(top["z"]).astype(np.int64).reshape(-1)
-    n = z.shape[0]
-    ref_xyz = np.asarray(ref["xyz"], dtype=np.float32)
-    if ref_xyz.ndim != 3 or ref_xyz.shape[1:] != (n, 3):
-        raise SystemExit(f"{args.ref}: xyz is {ref_xyz.shape}, the topology has {n} atoms")
-    if ref_xyz.shape[0] < 2:
-        raise SystemExit(f"{args.ref}: at least two reference frames are needed")
-    gen_xyz = np.asarray(_npz(args.gen, ["xyz"])["xyz"], dtype=np.float32)
-    if gen_xyz.ndim not in (3, 4) or gen_xyz.shape[-2:] != (n, 3):
-        raise SystemExit(f"{args.gen}: xyz is {gen_xyz.shape}, the topology has {n} atoms")
+    ref_xyz, gen_xyz, z, top, _ = compare_cli.read_sets(args)
     bonds = np.asarray(top["bonds"])
-    try:
+    with compare_cli.refusing():
         don_h, _, acc = donors_acceptors(z, bonds)
         lim = limits()
         if don_h.shape[0] > lim["hydrogens"] or acc.shape[0] > lim["acceptors"]:
             raise ValueError(f"the table is {don_h.shape[0]} donor hydrogens x {acc.shape[0]} acceptors "
                              f"(the kernel holds {lim['hydrogens']} x {lim['acceptors']})")
-    except ValueError as err:
-        raise SystemExit(str(err))
-    return {"ref_xyz": ref_xyz, "gen_xyz": gen_xyz.reshape(-1, n, 3), "z": z, "bonds": bonds}
+    return {"ref_xyz": ref_xyz, "gen_xyz": gen_xyz, "z": z, "bonds": bonds}
 
 
 def main(argv=None) -> dict:
     args = parser().parse_args(argv)
     inp = read_inputs(args)
     kw = dict(h_a_cutoff=args.hbond_cutoff, angle=args.hbond_angle, device=args.device)
-    try:
+    with compare_cli.refusing():
         stats = compare(inp["ref_xyz"], inp["gen_xyz"], inp["z"], inp["bonds"], native_occupancy=args.hbond_native, **kw)
         if args.bits:
             res = hbond_counts(inp["gen_xyz"], inp["z"], inp["bonds"], per_pair=True, **kw)
             np.savez(args.bits, bits=res["bits"], don_h=res["don_h"], don_d=res["don_d"], acc=res["acc"], bad=res["bad"])
-    except ValueError as err:
-        raise SystemExit(str(err))
-    with open(args.out, "w") as f:
-        json.dump(stats, f)
-    print(json.dumps({"hbond_stats": summary_of(stats), "out": args.out}), flush=True)
+    compare_cli.finish("hbond", stats, summary_of(stats), args.out)
     return stats
 
 

@@ -26,19 +26,16 @@ The full statistics of ``compare`` go to ``-out``, one JSON line with ``"sasa_st
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import os
 import sys
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
-from . import _lib, ensemble
+from . import _lib, compare_cli, ensemble
 from .ensemble import check_sets, device_of, groups_of, read_back, scalar_block, select_atoms, structures
 
-WORKSPACE_BYTES = 1 << 28              # structures_per_launch is lowered until the packed copy of a launch fits this
 BONDI_RADII = {1: 1.20, 6: 1.70, 7: 1.55, 8: 1.52, 9: 1.47, 15: 1.80, 16: 1.80, 17: 1.75}   # by atomic number (Bondi 1964)
 POLARITY = ("apolar", "polar")         # what the labels of ``polarity`` mean
 
@@ -136,7 +133,7 @@ def sasa_counts(xyz, z, sel=None, probe: float = 1.4, n_points: int = 256, radii
         raise ValueError(f"{C} distinct (class, radius) pairs (the kernel holds {lim['classes']})")
     u = sphere_points(P)
     dev = device_of(x, device)
-    M = max(1, min(int(structures_per_launch), lim["structures"], max(64, WORKSPACE_BYTES // (16 * m + 4))))
+    M = ensemble.structures_per_launch(structures_per_launch, lim["structures"], 16 * m + 4)
     out = {"class_counts": torch.zeros(S, C, dtype=torch.int32, device=dev), "bad": torch.zeros(S, dtype=torch.int32, device=dev),
            "atom_sum": torch.zeros(m, dtype=torch.int64, device=dev), "atom_sumsq": torch.zeros(m, dtype=torch.int64, device=dev)}
     if per_atom:
@@ -145,8 +142,7 @@ def sasa_counts(xyz, z, sel=None, probe: float = 1.4, n_points: int = 256, radii
         lib = _lib.load()
         d_sel, d_r, d_u, d_cls = (torch.from_numpy(a).to(dev) for a in (table, r, u, cls))
         ws = ensemble.workspace(int(lib.cgv_sasa_workspace_bytes(min(M, S), m, P)), dev)
-        for start in range(0, S, M):
-            chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+        for start, chunk in ensemble.chunks(x, M, dev):
             k = int(chunk.shape[0])
             _lib.call("cgv_sasa_counts", _lib.ptr(chunk), _lib.ptr(d_sel), _lib.ptr(d_r), _lib.ptr(d_u), _lib.ptr(d_cls), k, n, m, P, C,
                       _lib.ptr(out["counts"][start:start + k]) if per_atom else None, _lib.ptr(out["class_counts"][start:start + k]),
@@ -264,12 +260,9 @@ def compare_from_counts(even: dict, odd: dict, gen: dict, labels=None, groups=No
             lo, hi = float(both.min()), float(both.max())
             pad = 0.1 * (hi - lo) if hi > lo else 0.05 * max(abs(hi), 1.0)       # the reference's range, 20 % wider
             blocks[key] = scalar_block(se[key], so[key], sg[key], lo - pad, hi + pad, n_bins)
-    n_of = lambda *rs: int(sum(np.asarray(r["bad"]).shape[0] for r in rs))
-    n_bad = lambda *rs: int(sum(np.asarray(r["bad"], dtype=bool).sum() for r in rs))
     floor = {"profile_rmse": f_rmse, "profile_max_dev": f_max}
     floor.update({key + "_jsd": blocks[key]["floor"] if blocks[key] else None for key in blocks})
-    return {"n_ref": n_of(even, odd), "n_gen": n_of(gen), "n_bad_ref": n_bad(even, odd), "n_bad_gen": n_bad(gen),
-            "params": dict(params or {}, n_bins=int(n_bins)), "labels": rows,
+    return {**ensemble.set_sizes(even, odd, gen), "params": dict(params or {}, n_bins=int(n_bins)), "labels": rows,
             "mean_ref": None if p_ref is None else p_ref.tolist(), "mean_gen": None if p_gen is None else p_gen.tolist(),
             "profile_rmse": rmse, "profile_max_dev": max_dev, "floor": floor, "top_atoms": top, **blocks}
 
@@ -309,42 +302,27 @@ def compare(ref_xyz, gen_xyz, z, bonds, atoms="all", probe: float = 1.4, n_point
 
 SASA_STATS_KEYS = ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "params", "labels", "mean_ref", "mean_gen", "profile_rmse",
                    "profile_max_dev", "floor", "top_atoms", "total", "apolar", "apolar_fraction")
-_MOMENTS = ("jsd", "mean_ref", "std_ref", "mean_gen", "std_gen")
 
 
 def summary_of(stats: dict) -> dict:
     """What the command line puts under ``"sasa_stats"`` in its JSON summary line: no profiles, no histograms."""
     short = {k: stats[k] for k in ("n_ref", "n_gen", "n_bad_ref", "n_bad_gen", "profile_rmse", "profile_max_dev", "floor")}
     for k in ("total", "apolar", "apolar_fraction"):
-        short[k] = None if stats[k] is None else {name: stats[k][name] for name in _MOMENTS}
+        short[k] = ensemble.short_block(stats[k])
     return short
 
 
 # ----------------------------------------------------------------------------- command line
 def parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="python -m coarsegrainingvae_amd.sasa",
-                                description="solvent-accessible surface area of generated structures against a reference")
-    p.add_argument("-gen", required=True, help="npz with xyz [T,K,n,3] or [S,n,3]: the generated structures (backmap -out)")
-    p.add_argument("-ref", required=True, help="npz with xyz [T,n,3]: the reference frames, at least two")
-    p.add_argument("-top", default=None, help="npz with z and bonds (and mapping); default: those of -ref")
+    p = compare_cli.base_parser("python -m coarsegrainingvae_amd.sasa",
+                                "solvent-accessible surface area of generated structures against a reference",
+                                top_help="npz with z and bonds (and mapping); default: those of -ref")
     p.add_argument("-sasa_atoms", choices=("all", "heavy"), default="all", help="the atoms that make up the molecule (all)")
     p.add_argument("-sasa_probe", type=float, default=1.4, help="probe radius in Angstrom (1.4)")
     p.add_argument("-sasa_points", type=int, default=256, help="sphere points per atom (256)")
     p.add_argument("-sasa_groups", choices=("none", "bead", "residue"), default="none",
                    help="profile over atoms (none), beads of the mapping, or residues of a peptide (none)")
-    p.add_argument("-out", default="sasa_stats.json", help="where the full statistics go (sasa_stats.json)")
-    p.add_argument("-device", default="cuda")
-    return p
-
-
-def _npz(path: str, need) -> dict:
-    if not os.path.exists(path):
-        raise SystemExit(f"{path}: no such file")
-    with np.load(path, allow_pickle=False) as f:
-        missing = sorted(set(need) - set(f.files))
-        if missing:
-            raise SystemExit(f"{path}: missing {missing}")
-        return {k: f[k] for k in f.files}
+    return compare_cli.finish_parser(p, "sasa_stats.json")
 
 
 def read_inputs(args) -> dict:
@@ -354,49 +332,27 @@ def read_inputs(args) -> dict:
         raise SystemExit("-sasa_probe must be a finite length >= 0 in Angstrom")
     if args.sasa_points < 1:
         raise SystemExit("-sasa_points must be at least 1")
-    ref = _npz(args.ref, ["xyz"])
-    top = _npz(args.top, ["z", "bonds"]) if args.top else ref
-    if "z" not in top or "bonds" not in top:
-        raise SystemExit(f"{args.ref}: missing z / bonds (or pass -top)")
-    z = np.asarray(top["z"]).astype(np.int64).reshape(-1)
-    n = z.shape[0]
-    ref_xyz = np.asarray(ref["xyz"], dtype=np.float32)
-    if ref_xyz.ndim != 3 or ref_xyz.shape[1:] != (n, 3):
-        raise SystemExit(f"{args.ref}: xyz is {ref_xyz.shape}, the topology has {n} atoms")
-    if ref_xyz.shape[0] < 2:
-        raise SystemExit(f"{args.ref}: at least two reference frames are needed")
-    gen_xyz = np.asarray(_npz(args.gen, ["xyz"])["xyz"], dtype=np.float32)
-    if gen_xyz.ndim not in (3, 4) or gen_xyz.shape[-2:] != (n, 3):
-        raise SystemExit(f"{args.gen}: xyz is {gen_xyz.shape}, the topology has {n} atoms")
-    gen_xyz = gen_xyz.reshape(-1, n, 3)
+    ref_xyz, gen_xyz, z, top, ref = compare_cli.read_sets(args)
     mapping = top.get("mapping", ref.get("mapping"))
     groups = None if args.sasa_groups == "none" else args.sasa_groups
     sel = select_atoms(z, args.sasa_atoms)
     if sel.shape[0] == 0:
         raise SystemExit(f"the topology has no {args.sasa_atoms} atoms")
-    try:
+    with compare_cli.refusing():
         radii_of(z, sel)
-    except ValueError as err:
-        raise SystemExit(str(err))
     if groups is not None:
-        try:
+        with compare_cli.refusing(f"-sasa_groups {groups}: "):
             groups_of(z, top["bonds"], mapping, groups)
-        except ValueError as err:
-            raise SystemExit(f"-sasa_groups {groups}: {err}")
     return {"ref_xyz": ref_xyz, "gen_xyz": gen_xyz, "z": z, "bonds": np.asarray(top["bonds"]), "mapping": mapping, "groups": groups}
 
 
 def main(argv=None) -> dict:
     args = parser().parse_args(argv)
     inp = read_inputs(args)
-    try:
+    with compare_cli.refusing():
         stats = compare(inp["ref_xyz"], inp["gen_xyz"], inp["z"], inp["bonds"], atoms=args.sasa_atoms, probe=args.sasa_probe,
                         n_points=args.sasa_points, groups=inp["groups"], mapping=inp["mapping"], device=args.device)
-    except ValueError as err:
-        raise SystemExit(str(err))
-    with open(args.out, "w") as f:
-        json.dump(stats, f)
-    print(json.dumps({"sasa_stats": summary_of(stats), "out": args.out}), flush=True)
+    compare_cli.finish("sasa", stats, summary_of(stats), args.out)
     return stats
 
 

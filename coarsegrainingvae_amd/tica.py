@@ -268,8 +268,7 @@ def project(xyz, model: TicaModel, structures_per_launch: int = 16384, device="c
         total = torch.zeros(nb, nb, dtype=torch.int64, device=dev)
         total_out = torch.zeros(1, dtype=torch.int64, device=dev)
     M = max(int(structures_per_launch), 1)
-    for start in range(0, S, M):
-        chunk = x[start:start + M].detach().to(dev, torch.float32).contiguous()
+    for start, chunk in ensemble.chunks(x, M, dev):
         if hist is not None and start:
             counts.zero_(), outside.zero_()
         project_launch(chunk, ptab, mean, W, ics[start:start + M] if want_ics else None,

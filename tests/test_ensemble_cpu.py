@@ -4,6 +4,7 @@ import re
 
 import numpy as np
 import pytest
+import torch
 
 from coarsegrainingvae_amd import backmap as bm, ensemble, run_ala
 from coarsegrainingvae_amd.analyses import ANALYSES
@@ -104,6 +105,56 @@ def test_hist_moments_and_scalar_block_on_fixed_arrays():
     assert block["std_ref"] == pytest.approx(np.std([0.1, 0.6, 0.1, 0.9])) and block["std_gen"] == pytest.approx(np.std(gen))
     empty = ensemble.scalar_block(np.zeros(0), np.zeros(0), gen, 0.0, 1.0, 2)
     assert empty["mean_ref"] is None and empty["std_ref"] is None and empty["jsd"] is None and empty["floor"] is None
+
+
+@pytest.mark.parametrize("S, M", ((0, 4), (3, 4), (4, 4), (9, 4)))                    # nothing, S < M, S = M, S = 2M + 1
+def test_chunks_cover_the_set_in_order_as_contiguous_fp32(S, M):
+    x = torch.arange(S * 5 * 3, dtype=torch.float64).reshape(5, S, 3).transpose(0, 1)         # float64 and not contiguous
+    got = list(ensemble.chunks(x, M, "cpu"))
+    assert [start for start, _ in got] == list(range(0, S, M)) and len(got) == -(-S // M)
+    for start, chunk in got:
+        assert chunk.dtype == torch.float32 and chunk.is_contiguous() and chunk.device.type == "cpu"
+        assert tuple(chunk.shape) == (min(M, S - start), 5, 3) and not chunk.requires_grad
+    if S:
+        assert torch.equal(torch.cat([chunk for _, chunk in got]), x.to(torch.float32))
+    grad = torch.zeros(3, 5, 3, requires_grad=True)
+    assert not any(chunk.requires_grad for _, chunk in ensemble.chunks(grad, 2, "cpu"))
+
+
+def test_structures_per_launch_is_the_rule_the_three_callers_wrote_out():
+    assert ensemble.WORKSPACE_BYTES == 1 << 28
+    m, nH, nA = 5000, 1500, 2000
+    for per in (16 * m, 16 * m + 4, 16 * (2 * nH + nA)):                      # contacts, sasa, hbonds
+        budget = (1 << 28) // per
+        assert 64 < budget < 4096                                             # so that all three bounds are exercised
+        for requested, limit in ((budget - 1, 1 << 20), (4096, 1 << 20), (4096, 100), (budget + 5, budget + 1), (0, 4096), (-3, 4096)):
+            want = max(1, min(int(requested), limit, max(64, (1 << 28) // per)))
+            assert ensemble.structures_per_launch(requested, limit, per) == want, (requested, limit, per)
+    assert ensemble.structures_per_launch(3001, 1 << 20, 16 * m) == 3001      # below the budget: the request
+    assert ensemble.structures_per_launch(1 << 30, 1 << 20, 16 * m) == (1 << 28) // (16 * m)   # above it: the budget
+    assert ensemble.structures_per_launch(4096, 100, 16 * m) == 100           # above the limit
+    assert ensemble.structures_per_launch(0, 4096, 16 * m) == 1
+    assert ensemble.structures_per_launch(4096, 4096, 1 << 27) == 64          # the budget never asks for fewer than 64
+
+
+def test_set_sizes_counts_structures_and_bad_ones():
+    even, odd = {"bad": np.array([False, True, False])}, {"bad": np.array([0, 0], dtype=np.int32)}
+    gen = {"bad": [True, True, False, False, True]}
+    got = ensemble.set_sizes(even, odd, gen)
+    assert got == {"n_ref": 5, "n_gen": 5, "n_bad_ref": 1, "n_bad_gen": 3} and list(got) == ["n_ref", "n_gen", "n_bad_ref", "n_bad_gen"]
+    assert all(type(v) is int for v in got.values())
+    empty = {"bad": np.zeros(0, dtype=bool)}
+    assert ensemble.set_sizes(empty, empty, empty) == {"n_ref": 0, "n_gen": 0, "n_bad_ref": 0, "n_bad_gen": 0}
+
+
+def test_short_block_keeps_the_moments():
+    assert ensemble.MOMENTS == ("jsd", "mean_ref", "std_ref", "mean_gen", "std_gen")
+    assert ensemble.short_block(None) is None and ensemble.short_block(None, ("jsd",)) is None
+    block = ensemble.scalar_block(np.array([0.1, 0.6]), np.array([0.1, 0.9]), np.array([0.1, 0.1, 0.6, 1.2]), 0.0, 1.0, 2)
+    short = ensemble.short_block(block)
+    assert list(short) == list(ensemble.MOMENTS) and all(short[k] == block[k] for k in short)
+    flex = ensemble.short_block(block, ("jsd", "floor") + ensemble.MOMENTS[1:])
+    assert list(flex) == ["jsd", "floor", "mean_ref", "std_ref", "mean_gen", "std_gen"] and flex["floor"] == block["floor"]
 
 
 def test_every_record_has_its_switch_in_both_command_lines():
