@@ -246,6 +246,11 @@ PROTOTYPES = {
     "cgv_hbond_chunk": (_i, []),
     "cgv_hbond_workspace_bytes": (_sz, [_i, _i, _i]),
     "cgv_hbond_counts": (_i, [_p] * 6 + [_i, _i, _i, _i, _f, _f] + [_p] * 5 + [_p, _sz, _p]),
+    "cgv_dssp_max_residues": (_i, []),
+    "cgv_dssp_max_structures": (_i, []),
+    "cgv_dssp_wave_path_max": (_i, []),
+    "cgv_dssp_bend_c2": (_f, []),
+    "cgv_dssp_assign": (_i, [_p] * 4 + [_i, _i, _i] + [_p] * 5 + [_p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

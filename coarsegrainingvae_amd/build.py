@@ -30,7 +30,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # kernel's rotation solve (csrc/superpose_rot.h) is the text a host program compiles to measure it against LAPACK; the
 # surface kernel builds a sphere point as a rounded product plus a rounded sum and tests sq_dist2 against a rounded r * r,
 # all restated on the host bit for bit; the hydrogen-bond kernel tests sq_dist2 against a cutoff and the square of a rounded
-# dot product against a rounded product of three, restated the same way.
+# dot product against a rounded product of three, restated the same way; the secondary-structure kernel places a virtual
+# hydrogen by a rounded square root and quotient and tests a sum of four rounded reciprocal distances, a sq_dist2 and a bend
+# like the hydrogen-bond angle, all restated bit for bit.
 # kde.hip has NO entry: its fp32 stage sums are checked against an error bound, not restated bit for bit, and its one
 # contraction that matters (the minimum image) is written as an explicit fmaf -- the default flags do; cluster.hip has none
 # either: its only floating-point operation is a comparison of doubles that K17 wrote
@@ -38,7 +40,8 @@ SOURCE_FLAGS = {"newman.hip": ["-ffp-contract=off"], "baseline.hip": ["-ffp-cont
                 "sample_quality.hip": ["-ffp-contract=off"], "ensemble_check.hip": ["-ffp-contract=off"],
                 "internal_hist.hip": ["-ffp-contract=off"], "tica.hip": ["-ffp-contract=off"],
                 "contact_map.hip": ["-ffp-contract=off"], "align_mean.hip": ["-ffp-contract=off"],
-                "sasa.hip": ["-ffp-contract=off"], "hbond.hip": ["-ffp-contract=off"]}
+                "sasa.hip": ["-ffp-contract=off"], "hbond.hip": ["-ffp-contract=off"],
+                "dssp.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

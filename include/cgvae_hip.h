@@ -1446,6 +1446,64 @@ int cgv_hbond_counts(const float* xyz, const int32_t* don_h /*[nH]*/, const int3
                      int32_t* n_hbonds /*[S]*/, int32_t* n_native /*[S]*/, int32_t* bad /*[S]*/,
                      uint64_t* bits /*[S,nH,W] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K26  secondary structure of an ensemble (DSSP, Kabsch & Sander 1983) -- which residues are helix, strand, turn or bend:
+ * per structure the class of every residue and the residues of every class, and over the structures how often every
+ * residue is in every class.  Backbone heavy atoms only (the amide H is virtual).  Nothing in the reference computes it.
+ * Lengths in Angstrom.
+ *   xyz [n_structures,n_atoms,3] fp32
+ *   res [n_residues,4] int32                  N, CA, C, O of residue r, the residues in chain order: the CALLER's tables
+ *   prev [n_residues,2] int32                 the carbonyl C' bonded to N(r) and its O'; -1, -1: the residue has no amide
+ *                                             hydrogen and never donates (a chain start, a proline)
+ *   link [n_residues] int32                   1 iff C(r) is bonded to N(r+1); link[n_residues - 1] is taken as 0.
+ *                                             An atom index outside [0, n_atoms) reads atom 0 (the host wrapper builds the
+ *                                             tables itself); nothing is read out of bounds.
+ * All of it in fp32 with every operation individually rounded (no fma; sqrtf and / correctly rounded), every test written so
+ * that a NaN fails it:
+ *   virtual hydrogen  w = C' - O',  l = sqrtf((wx*wx + wy*wy) + wz*wz),  H_k = N_k + w_k / l
+ *   hb[i][j]          C=O of i accepts from N-H of j: j has an H, j != i, j != i + 1, sq_dist2(CA_i, CA_j) < 81 and e < -0.5
+ *                     with e = 27.888 * (((1/rON + 1/rCH) - 1/rOH) - 1/rCN), r = sqrtf(sq_dist2), and e = -9.9 when one of the
+ *                     four squared distances is < 0.25
+ *   cont(a, b)        link[a .. b-1] are all 1
+ *   turn_n(i)         hb[i][i+n] and cont(i, i+n), n = 3, 4, 5
+ *   bridge (i, j)     |i-j| >= 3, i+-1 and j+-1 exist, cont(i-1, i+1), cont(j-1, j+1);
+ *                     par = (hb[i-1][j] & hb[j][i+1]) | (hb[j-1][i] & hb[i][j+1]),
+ *                     anti = (hb[i][j] & hb[j][i]) | (hb[i-1][j+1] & hb[j-1][i+1]);  in a ladder when the same type also holds
+ *                     at (i+1, j+1) or (i-1, j-1) (par), at (i+1, j-1) or (i-1, j+1) (anti)
+ *   bend(i)           cont(i-2, i+2), u = CA_i - CA_{i-2}, v = CA_{i+2} - CA_i: uu > 0, vv > 0 and (dot <= 0 or
+ *                     dot*dot < (c2*uu)*vv), c2 = cgv_dssp_bend_c2() = fp32(cos(70 degrees)^2)
+ *   classes, each stage reading only finished earlier ones, code = index into "HBEGITS-":
+ *                     H  i..i+3 where turn_4(i-1) & turn_4(i);  E  not H, a bridge that is in a ladder;  B  not H, a bridge
+ *                     but none in a ladder;  G  i..i+2 where turn_3(i-1) & turn_3(i), none of the three H E B;  I  i..i+4
+ *                     likewise for n = 5, none of the five H E B G;  T  unassigned and turn_n(i-k), 1 <= k < n;  S  unassigned
+ *                     and bend;  -  otherwise
+ * A host that restates the arithmetic gets every integer below exactly; no floating-point result leaves the device.
+ *   class_counts [n_residues,8] int64         ADDED to: in how many good structures of this call residue r has class c; a
+ *                                             caller cuts a long ensemble into launches and zeroes it once
+ *   n_class [n_structures,8] int32            overwritten: the residues of every class (a row sums to n_residues)
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate in an atom of res
+ *                                             or prev.  Its n_class row is -1, its codes are 255, its hb_bits 0; it enters
+ *                                             no sum.
+ *   codes [n_structures,n_residues] uint8 or NULL   overwritten: the class of every residue
+ *   hb_bits [n_structures,n_residues,W] uint64 or NULL, W = ceil(n_residues / 64)   overwritten: bit (j & 63) of word j >> 6 of
+ *                                             row i is hb[i][j]; bits past n_residues are 0
+ * Launches: ONE.  The whole assignment of a structure stays in LDS -- N CA C O H of every residue, hb and its transpose as
+ *   bits, the per-residue flags; nothing [S,R,R] reaches memory but hb_bits.  n_residues <= cgv_dssp_wave_path_max(): a wave
+ *   owns a structure, four a block, the blocks walk the structures and gather class_counts in LDS.  Beyond: a block owns a
+ *   structure.  Either way a lane owns a donor and the wave's ballot of the test is the word of hb; bridges and ladders are
+ *   ANDs of shifted words.  Integer sums meet in atomicAdd: the same bits on every call, however the structures are cut.
+ * No workspace.
+ * Limits: 1 <= n_residues <= cgv_dssp_max_residues() -- 384: what 64 KB of LDS hold of 16 R W + 8 W + 67 R + 64 bytes -- and
+ *   n_structures <= cgv_dssp_max_structures() per launch; beyond a limit the call fails (CGV_E_BADARG) with its reason before
+ *   any launch.  See DESIGN.md (K26 row). */
+int cgv_dssp_max_residues(void);
+int cgv_dssp_max_structures(void);
+int cgv_dssp_wave_path_max(void);
+float cgv_dssp_bend_c2(void);
+int cgv_dssp_assign(const float* xyz, const int32_t* res /*[R,4]*/, const int32_t* prev /*[R,2]*/, const int32_t* link /*[R]*/,
+                    int n_structures, int n_atoms, int n_residues, int64_t* class_counts /*[R,8]*/, int32_t* n_class /*[S,8]*/,
+                    int32_t* bad /*[S]*/, uint8_t* codes /*[S,R] or NULL*/, uint64_t* hb_bits /*[S,R,W] or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
