@@ -251,6 +251,15 @@ PROTOTYPES = {
     "cgv_dssp_wave_path_max": (_i, []),
     "cgv_dssp_bend_c2": (_f, []),
     "cgv_dssp_assign": (_i, [_p] * 4 + [_i, _i, _i] + [_p] * 5 + [_p]),
+    "cgv_pca_max_features": (_i, []),
+    "cgv_pca_max_atoms": (_i, []),
+    "cgv_pca_max_structures": (_i, []),
+    "cgv_pca_max_components": (_i, []),
+    "cgv_pca_max_bins2": (_i, []),
+    "cgv_pca_moments_splits": (_i, [_i, _i]),
+    "cgv_pca_moments_workspace_bytes": (_sz, [_i, _i]),
+    "cgv_pca_moments": (_i, [_p] * 4 + [_i] * 3 + [_p] * 3 + [_p, _sz, _p]),
+    "cgv_pca_project": (_i, [_p] * 6 + [_i] * 4 + [_p, _i, _i, _i] + [C.c_double] * 4 + [_p] * 3),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

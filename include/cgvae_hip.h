@@ -1504,6 +1504,64 @@ int cgv_dssp_assign(const float* xyz, const int32_t* res /*[R,4]*/, const int32_
                     int n_structures, int n_atoms, int n_residues, int64_t* class_counts /*[R,8]*/, int32_t* n_class /*[S,8]*/,
                     int32_t* bad /*[S]*/, uint8_t* codes /*[S,R] or NULL*/, uint64_t* hb_bits /*[S,R,W] or NULL*/, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K27  Cartesian principal component analysis of a superposed ensemble ("essential dynamics", Amadei et al. 1993; what
+ * gmx covar / gmx anaeig do) -- in which directions the atoms move TOGETHER.  Nothing in the reference computes it.
+ * Both entry points read what K21 writes for a chunk of structures and never superpose anything themselves:
+ *   y [n_structures,n_atoms,3] fp32           K21's `aligned`: the structures superposed onto a target
+ *   bad [n_structures] int32                  K21's `bad`: a structure with bad[s] != 0 contributes nothing (its y is NaN
+ *                                             and is never multiplied: all its features are staged as +0.0)
+ *   sel [m] int32                             the atoms analysed, d = 3 m features.  An index outside [0, n_atoms) reads
+ *                                             atom 0 (the host wrapper refuses such tables); nothing is read out of bounds.
+ *   centre [n_atoms,3] fp64                   the point the sums are taken about: the caller passes the superposition
+ *                                             target in the frame of y (its selected atoms' centroid at the origin), which
+ *                                             is close to the mean, so nothing cancels when the covariance is formed
+ * Feature:  f[3a + c] = (double)y[s, sel[a], c] - centre[sel[a], c],  a < m, c < 3.  The widening is exact and the
+ * subtraction one fp64 rounding (no FMA contraction), so a host restatement holds the same bits.  No [n_structures, d]
+ * feature tensor exists in memory.
+ *
+ * cgv_pca_moments ADDS, over the good structures, to the caller's buffers (zeroed by the caller before the first call)
+ *   sum [d] fp64 += sum f      cov [d,d] fp64 += sum f f^T (full, exactly symmetric)      n_good [1] int32 += their number
+ * Two launches: grid (tile pairs bi <= bj of 32 features, cgv_pca_moments_splits() structure ranges) x 256 threads, a
+ * block stages 16 structures of its tiles' features in LDS as fp64 and accumulates F_i^T F_j in registers with
+ * v_mfma_f64_16x16x4_f64 (the product is not rounded), diagonal blocks also sum their features in ascending structure
+ * order; every block writes its tile to its range's slice of the workspace; the second launch sums the ranges in
+ * ascending order into the totals and fills cov below the diagonal from above it.  No floating-point atomics: the order of
+ * every addition is a function of (n_structures, d) alone -- the same bits on every run.  The ranges aim at about four
+ * blocks per CU (K16's rule).
+ * workspace: cgv_pca_moments_workspace_bytes(n_structures, d) bytes, 8-byte aligned, contents need not survive.
+ *
+ * cgv_pca_project: the structures onto k modes, mean [d] and W [d,k] fp64, 1 <= k <= cgv_pca_max_components() (8).  One
+ * launch, one wave per structure.
+ *   proj [n_structures,k] fp64 (may be NULL)  OVERWRITTEN: proj[s,c] = sum_f (f_s[f] - mean[f]) * W[f,c] (mean is passed,
+ *                         not folded into an offset: two roundings per feature, restated bit for bit); each lane sums
+ *                         features lane, lane + 64, .. in ascending order, a fixed xor tree combines the lanes (same bits
+ *                         every run).  NaN for a bad structure.
+ *   counts [n_bins2,n_bins2] int32, outside [1] int32 (both or neither; ZEROED BY THE CALLER, the launch ADDS)
+ *                         the joint histogram of components (comp_a, comp_b), K16's bin rule: bin = floor((v - lo) *
+ *                         n_bins2 / (hi - lo)) in fp64 for lo <= v < hi, clamped to [0, n_bins2); counts[bin_a, bin_b]; a
+ *                         structure with either component outside its range or non-finite, and every bad structure,
+ *                         counts once in outside.  LDS integer atomics, one integer vector atomic per non-zero slot.
+ * Limits, each refused (CGV_E_BADARG) with its reason before any launch:
+ *   3 m <= cgv_pca_max_features() -- 2048: bounded by total plus workspace bytes, a [d,d] fp64 total is 32 MB there and the
+ *   workspace of a launch as much again (below 1409 features the ranges' slices together stay under 34 MB); m = 512 fits --
+ *   n_atoms <= cgv_pca_max_atoms(), n_structures <= cgv_pca_max_structures() per launch, k <= cgv_pca_max_components(),
+ *   1 <= n_bins2 <= cgv_pca_max_bins2(), lo < hi finite.  Bound: see DESIGN.md (K27 row). */
+int cgv_pca_max_features(void);
+int cgv_pca_max_atoms(void);
+int cgv_pca_max_structures(void);
+int cgv_pca_max_components(void);
+int cgv_pca_max_bins2(void);
+int cgv_pca_moments_splits(int n_structures, int d);                 /* structure ranges of a call; 0: the call adds nothing */
+size_t cgv_pca_moments_workspace_bytes(int n_structures, int d);
+int cgv_pca_moments(const float* y, const int32_t* sel /*[m]*/, const double* centre /*[n_atoms,3]*/, const int32_t* bad,
+                    int n_structures, int n_atoms, int m, double* sum /*[3m]*/, double* cov /*[3m,3m]*/, int32_t* n_good,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int cgv_pca_project(const float* y, const int32_t* sel /*[m]*/, const double* centre /*[n_atoms,3]*/, const int32_t* bad,
+                    const double* mean /*[3m]*/, const double* W /*[3m,k]*/, int n_structures, int n_atoms, int m, int k,
+                    double* proj /*[n_structures,k]*/, int comp_a, int comp_b, int n_bins2, double lo_a, double hi_a, double lo_b,
+                    double hi_b, int32_t* counts, int32_t* outside, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
