@@ -65,6 +65,59 @@ def chunks(x: torch.Tensor, M: int, dev) -> Iterator[Tuple[int, torch.Tensor]]:
         yield start, x[start:start + M].detach().to(dev, torch.float32).contiguous()
 
 
+# ----------------------------------------------------------------------------- the map of two components (tica, pca)
+def check_hist2(spec, k: int, lim: Dict[str, int], bins_name: str = "n_bins2"):
+    """``(comp_a, comp_b, n_bins2, (lo_a, hi_a), (lo_b, hi_b))`` of a projection onto ``k`` components as plain numbers, or
+    ``ValueError``: more bins than the family's ``lim["bins2"]``, a component outside ``[0, k)``, a range without ``lo < hi``."""
+    ca, cb, nb, ra, rb = spec[:5]
+    if not 1 <= int(nb) <= lim["bins2"]:
+        raise ValueError(f"{bins_name} must be in 1..{lim['bins2']}")
+    if not (0 <= int(ca) < k and 0 <= int(cb) < k):
+        raise ValueError(f"the histogram's components must be in [0, {k})")
+    if not (float(ra[0]) < float(ra[1]) and float(rb[0]) < float(rb[1])):
+        raise ValueError("histogram ranges must be (lo, hi) with lo < hi")
+    return int(ca), int(cb), int(nb), (float(ra[0]), float(ra[1])), (float(rb[0]), float(rb[1]))
+
+
+def hist2_args(hist, k: int, lim: Dict[str, int]) -> tuple:
+    """The nine trailing arguments of ``cgv_tica_project`` / ``cgv_pca_project`` from what a ``project_launch`` is handed:
+    ``None`` (no histogram) or ``(*spec, counts [nb,nb] int32, outside [1] int32)``, checked (``check_hist2``)."""
+    if hist is None:
+        return 0, 0, 0, 0.0, 1.0, 0.0, 1.0, None, None
+    ca, cb, nb, ra, rb = check_hist2(hist, k, lim)
+    counts, outside = hist[5], hist[6]
+    if tuple(counts.shape) != (nb, nb) or counts.dtype != torch.int32 or outside.numel() != 1 or outside.dtype != torch.int32:
+        raise ValueError("counts [n_bins2, n_bins2] and outside [1] must be int32")
+    return ca, cb, nb, ra[0], ra[1], rb[0], rb[1], _lib.ptr(counts), _lib.ptr(outside)
+
+
+class Hist2:
+    """The map of two components over the launches of one ``project``: the kernel adds a launch's structures into an
+    int32 pair, the running totals are int64 (a set may hold more than 2^31 structures).  The spec is checked before
+    anything is allocated."""
+
+    def __init__(self, spec, k: int, lim: Dict[str, int], device, bins_name: str = "n_bins2"):
+        self.spec = check_hist2(spec, k, lim, bins_name)
+        nb = self.spec[2]
+        self.counts, self.outside = (torch.zeros(s, dtype=torch.int32, device=device) for s in ((nb, nb), (1,)))
+        self.total, self.total_out = (torch.zeros(s, dtype=torch.int64, device=device) for s in ((nb, nb), (1,)))
+        self.used = False
+
+    def launch(self, run) -> None:
+        """``run(hist)`` is one ``project_launch``: the int32 pair is zeroed before every launch after the first and
+        added to the totals after it."""
+        if self.used:
+            self.counts.zero_(), self.outside.zero_()
+        self.used = True
+        run((*self.spec, self.counts, self.outside))
+        self.total += self.counts
+        self.total_out += self.outside
+
+    def totals(self) -> List[torch.Tensor]:
+        """``[counts [nb,nb], outside [1]]`` int64, to append to the one ``read_back``."""
+        return [self.total, self.total_out]
+
+
 # ----------------------------------------------------------------------------- selections and sets
 def selection(sel, n_atoms: int, *, purpose: str, at_least: int = 1, unique: bool = True,
               max_atoms: Optional[int] = None) -> np.ndarray:

@@ -143,25 +143,11 @@ def project_launch(y: torch.Tensor, sel: torch.Tensor, centre: torch.Tensor, bad
         raise ValueError(f"a launch projects onto 1..{lim['components']} modes, W has {k}")
     if proj is not None and (tuple(proj.shape) != (S, k) or proj.dtype != torch.float64):
         raise ValueError(f"proj must be [{S}, {k}] float64")
-    if hist is None:
-        ca = cb = nb = 0
-        ra = rb = (0.0, 1.0)
-        counts = outside = None
-    else:
-        ca, cb, nb, ra, rb, counts, outside = hist
-        if not 1 <= int(nb) <= lim["bins2"]:
-            raise ValueError(f"n_bins2 must be in 1..{lim['bins2']}")
-        if not (0 <= int(ca) < k and 0 <= int(cb) < k):
-            raise ValueError(f"the histogram's components must be in [0, {k})")
-        if not (float(ra[0]) < float(ra[1]) and float(rb[0]) < float(rb[1])):
-            raise ValueError("histogram ranges must be (lo, hi) with lo < hi")
-        if tuple(counts.shape) != (nb, nb) or counts.dtype != torch.int32 or outside.numel() != 1 or outside.dtype != torch.int32:
-            raise ValueError("counts [n_bins2, n_bins2] and outside [1] must be int32")
+    args = ensemble.hist2_args(hist, k, lim)
     if S == 0:
         return
     _lib.call("cgv_pca_project", _lib.ptr(y), _lib.ptr(sel), _lib.ptr(centre), _lib.ptr(bad), _lib.ptr(mean), _lib.ptr(W), S, n, m, k,
-              _lib.ptr(proj), int(ca), int(cb), int(nb), float(ra[0]), float(ra[1]), float(rb[0]), float(rb[1]), _lib.ptr(counts),
-              _lib.ptr(outside), _lib.stream_ptr(), tag="pca_project")
+              _lib.ptr(proj), *args, _lib.stream_ptr(), tag="pca_project")
 
 
 class _Chunks:
@@ -318,25 +304,15 @@ def project(model: PcaModel, xyz, components=(0, 1), ranges=None, n_bins: int = 
     mean = torch.from_numpy(np.ascontiguousarray(model.mu, dtype=np.float64)).to(p.dev)
     W = torch.from_numpy(np.ascontiguousarray(model.W, dtype=np.float64)).to(p.dev)
     proj = torch.empty(p.S, k, dtype=torch.float64, device=p.dev)
-    hist = total = total_out = None
+    acc = None
     if ranges is not None:
-        nb = int(n_bins)
-        ca, cb = (int(v) for v in components)
-        if not 1 <= nb <= limits()["bins2"]:
-            raise ValueError(f"n_bins must be in 1..{limits()['bins2']}")
-        counts, outside = torch.zeros(nb, nb, dtype=torch.int32, device=p.dev), torch.zeros(1, dtype=torch.int32, device=p.dev)
-        total, total_out = torch.zeros(nb, nb, dtype=torch.int64, device=p.dev), torch.zeros(1, dtype=torch.int64, device=p.dev)
-        hist = (ca, cb, nb, tuple(ranges[0]), tuple(ranges[1]), counts, outside)
+        acc = ensemble.Hist2((components[0], components[1], n_bins, ranges[0], ranges[1]), k, limits(), p.dev, bins_name="n_bins")
     for start, stop, y in c:
-        if hist is not None and start:
-            hist[5].zero_(), hist[6].zero_()
-        project_launch(y, p.sel, centre, p.bad[start:stop], mean, W, proj[start:stop], hist)
-        if hist is not None:
-            total += hist[5]
-            total_out += hist[6]
-    back = read_back([proj, p.bad] + ([total, total_out] if hist is not None else []))
-    return {"proj": np.array(back[0]), "bad": back[1].astype(bool), "hist2": np.array(back[2]) if hist is not None else None,
-            "outside": int(back[3][0]) if hist is not None else None}
+        run = lambda h: project_launch(y, p.sel, centre, p.bad[start:stop], mean, W, proj[start:stop], h)
+        acc.launch(run) if acc else run(None)
+    back = read_back([proj, p.bad] + (acc.totals() if acc else []))
+    return {"proj": np.array(back[0]), "bad": back[1].astype(bool), "hist2": np.array(back[2]) if acc else None,
+            "outside": int(back[3][0]) if acc else None}
 
 
 # ----------------------------------------------------------------------------- host statistics

@@ -227,17 +227,8 @@ def project_launch(xyz: torch.Tensor, pairs: torch.Tensor, mean: torch.Tensor, W
         raise ValueError("xyz must be float32, pairs int32, mean and W float64")
     if tuple(mean.shape) != (d,) or int(W.shape[0]) != d or (ics is not None and (tuple(ics.shape) != (S, k) or ics.dtype != torch.float64)):
         raise ValueError("mean [d], W [d,k], ics [S,k] float64")
-    if hist is None:
-        ca = cb = nb = 0
-        ra = rb = (0.0, 1.0)
-        counts = outside = None
-    else:
-        ca, cb, nb, ra, rb, counts, outside = hist
-        if tuple(counts.shape) != (nb, nb) or counts.dtype != torch.int32 or outside.numel() != 1 or outside.dtype != torch.int32:
-            raise ValueError("counts [n_bins2, n_bins2] and outside [1] must be int32")
-    _lib.call("cgv_tica_project", _lib.ptr(xyz), _lib.ptr(pairs), _lib.ptr(mean), _lib.ptr(W), S, n, d, k, _lib.ptr(ics), int(ca),
-              int(cb), int(nb), float(ra[0]), float(ra[1]), float(rb[0]), float(rb[1]), _lib.ptr(counts), _lib.ptr(outside),
-              _lib.stream_ptr(), tag="tica_project")
+    _lib.call("cgv_tica_project", _lib.ptr(xyz), _lib.ptr(pairs), _lib.ptr(mean), _lib.ptr(W), S, n, d, k, _lib.ptr(ics),
+              *ensemble.hist2_args(hist, k, limits()), _lib.stream_ptr(), tag="tica_project")
 
 
 def project(xyz, model: TicaModel, structures_per_launch: int = 16384, device="cuda", hist=None, want_ics: bool = True):
@@ -251,32 +242,17 @@ def project(xyz, model: TicaModel, structures_per_launch: int = 16384, device="c
     lim = limits()
     if not 1 <= k <= lim["components"]:
         raise ValueError(f"a launch projects onto 1..{lim['components']} components, the model has {k}")
-    if hist is not None and not 1 <= int(hist[2]) <= lim["bins2"]:
-        raise ValueError(f"n_bins2 must be in 1..{lim['bins2']}")
-    if hist is not None and not (float(hist[3][0]) < float(hist[3][1]) and float(hist[4][0]) < float(hist[4][1])):
-        raise ValueError("histogram ranges must be (lo, hi) with lo < hi")
     dev = device_of(x, device)
+    acc = None if hist is None else ensemble.Hist2(hist, k, lim, dev)
     ptab = torch.from_numpy(table).to(dev)
     mean = torch.from_numpy(np.ascontiguousarray(model.mean, dtype=np.float64)).to(dev)
     W = torch.from_numpy(np.ascontiguousarray(model.W, dtype=np.float64)).to(dev)
     ics = torch.zeros(S, k, dtype=torch.float64, device=dev) if want_ics else None
-    counts = outside = None
-    if hist is not None:
-        nb = int(hist[2])
-        counts = torch.zeros(nb, nb, dtype=torch.int32, device=dev)
-        outside = torch.zeros(1, dtype=torch.int32, device=dev)
-        total = torch.zeros(nb, nb, dtype=torch.int64, device=dev)
-        total_out = torch.zeros(1, dtype=torch.int64, device=dev)
     M = max(int(structures_per_launch), 1)
     for start, chunk in ensemble.chunks(x, M, dev):
-        if hist is not None and start:
-            counts.zero_(), outside.zero_()
-        project_launch(chunk, ptab, mean, W, ics[start:start + M] if want_ics else None,
-                       None if hist is None else (hist[0], hist[1], hist[2], hist[3], hist[4], counts, outside))
-        if hist is not None:
-            total += counts
-            total_out += outside
-    back = read_back(([ics] if want_ics else []) + ([total, total_out] if hist is not None else []))
+        run = lambda h: project_launch(chunk, ptab, mean, W, ics[start:start + M] if want_ics else None, h)
+        acc.launch(run) if acc else run(None)
+    back = read_back(([ics] if want_ics else []) + (acc.totals() if acc else []))
     out_ics = np.array(back[0]) if want_ics else None
     if hist is None:
         return out_ics

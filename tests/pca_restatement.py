@@ -1,7 +1,9 @@
 """Numpy restatement of K27 (csrc/pca.hip) and of the host statistics of ``coarsegrainingvae_amd.pca``, written from their
 definitions and importing nothing of the package: features with the same bits, moments by a plain ascending loop, the
-projection, the bin rule, DCCM, RMSIP and the covariance overlap."""
+projection, DCCM, RMSIP and the covariance overlap."""
 import numpy as np
+
+from gram_restatement import bin_of, edge_distance, hist2      # noqa: F401  (the bin rule, shared with K16)
 
 
 def features(y, sel, centre):
@@ -53,32 +55,6 @@ def project(y, sel, centre, mean, W, bad=None):
         proj += v[:, f:f + 1] * W[f][None]
     proj[~good] = np.nan
     return proj, np.abs(v) @ np.abs(W)
-
-
-def bin_of(v, lo, hi, nb):
-    """K16's rule: for ``lo <= v < hi`` the bin ``floor((v - lo) * nb / (hi - lo))`` in fp64, clamped to ``[0, nb)``; -1
-    otherwise (NaN included)."""
-    v = np.asarray(v, dtype=np.float64)
-    with np.errstate(invalid="ignore"):
-        inside = (v >= lo) & (v < hi)
-        b = np.floor((np.where(inside, v, lo) - lo) * float(nb) / (hi - lo)).astype(np.int64)
-    return np.where(inside, np.clip(b, 0, nb - 1), -1)
-
-
-def edge_distance(v, lo, hi, nb):
-    """How far ``v`` is from the nearest bin edge of ``[lo, hi)`` cut into ``nb`` bins (``lo`` and ``hi`` are edges)."""
-    v = np.asarray(v, dtype=np.float64)
-    edges = lo + (hi - lo) * np.arange(nb + 1) / nb
-    return np.abs(v[:, None] - edges[None]).min(1)
-
-
-def hist2(va, vb, ra, rb, nb):
-    """``(counts [nb,nb], outside)`` of the pairs ``(va, vb)``: a pair with either value off its range or NaN is outside."""
-    ia, ib = bin_of(va, ra[0], ra[1], nb), bin_of(vb, rb[0], rb[1], nb)
-    ok = (ia >= 0) & (ib >= 0)
-    counts = np.zeros((nb, nb), dtype=np.int64)
-    np.add.at(counts, (ia[ok], ib[ok]), 1)
-    return counts, int((~ok).sum())
 
 
 def covariance(mom):

@@ -163,7 +163,18 @@ def test_a_pair_table_with_an_atom_outside_the_frame_is_refused_before_any_launc
 # ----------------------------------------------------------------------------- projection
 @pytest.mark.parametrize("k,S", [(1, 1), (2, 1000), (8, 1000), (8, 1), (1, 1000), (2, 1)])
 def test_projection_and_its_histogram(k, S):
-    n, d, nb = 11, 50, 12
+    _projection_and_its_histogram(k, S, n=11, d=50)
+
+
+@pytest.mark.parametrize("k", [1, 8])
+def test_projection_where_a_lane_sums_three_features(k):
+    """d = 130 of the 136 pairs of 17 atoms: the lanes' strided loop runs up to three times (at d = 50 never twice).  The
+    bound d 2^-52 mass counts one rounding per product and per addition, so it holds for any d."""
+    _projection_and_its_histogram(k, 65, n=17, d=130)
+
+
+def _projection_and_its_histogram(k, S, n, d):
+    nb = 12
     rng = np.random.default_rng(100 * k + S)
     xyz, pairs = _frames(S, n, 20 + k + S), _pairs(n, d, seed=2)
     mean, W = rng.uniform(2, 6, d), rng.standard_normal((d, k))

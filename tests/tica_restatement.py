@@ -4,6 +4,8 @@ the device -- and everything after them in fp64, as sums over frames.  The fit i
 ``tica.fit_from_moments`` written on its own."""
 import numpy as np
 
+from gram_restatement import hist2
+
 
 def features(xyz, pairs):
     """``[T,d]`` float32 distances of the atom pairs, the kernel's operation order."""
@@ -71,16 +73,8 @@ def project(xyz, pairs, mean, W):
 
 def bin2(ics, ca, cb, nb, ra, rb):
     """Host binning of components: ``(counts [nb,nb], outside)``; ``floor((v - lo) * nb / (hi - lo))`` in that order."""
-    counts, outside = np.zeros((nb, nb), np.int64), 0
-    for row in np.asarray(ics, np.float64):
-        va, vb = row[ca], row[cb]
-        if not (ra[0] <= va < ra[1] and rb[0] <= vb < rb[1]):                   # False for a NaN
-            outside += 1
-            continue
-        ia = int(np.floor((va - ra[0]) * float(nb) / (ra[1] - ra[0])))
-        ib = int(np.floor((vb - rb[0]) * float(nb) / (rb[1] - rb[0])))
-        counts[min(max(ia, 0), nb - 1), min(max(ib, 0), nb - 1)] += 1
-    return counts, outside
+    ics = np.asarray(ics, np.float64)
+    return hist2(ics[:, ca], ics[:, cb], ra, rb, nb)
 
 
 def hinge_chain(T, seed=0, phi=0.995, jitter=0.05, frozen=False):
