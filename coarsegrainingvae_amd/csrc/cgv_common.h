@@ -62,6 +62,10 @@ __device__ inline void st3(float* p, float x, float y, float z) {
   *reinterpret_cast<f3*>(p) = t;
 }
 
+// An atom index out of a caller's table (a selection, a pair list, a residue table) is validated where it is used: an index
+// outside [0, n) reads atom 0, nothing is read out of bounds.
+__device__ __forceinline__ int sel_atom(int a, int n) { return (a >= 0 && a < n) ? a : 0; }
+
 // Dispatch a runtime n_rbf onto the compiled template instances.
 #define CGV_RBF_LIST(X) X(4) X(6) X(8) X(10) X(12) X(16) X(20)
 

@@ -28,7 +28,7 @@
 // same bits, and counts do not depend on how the caller cuts the structures into launches.
 #include <math.h>
 
-#include "cgv_common.h"
+#include "packed_dev.h"
 #include "sq_dist.h"
 
 namespace cgv {
@@ -39,13 +39,6 @@ constexpr int CT_CHUNK = 8;                  // structures staged at once: 8 x 1
 constexpr int CT_MAX_ATOMS = 1 << 14;        // selected atoms: counts [m,m] int32 is 1 GB there, m^2 / 2 pairs < 2^31
 constexpr int CT_MAX_STRUCTURES = 1 << 20;   // per launch
 constexpr int CT_MAX_GROUPS = 4096;          // the group kernel's grid is G x G waves
-constexpr int CT_TARGET_BLOCKS = 1024;       // 4 blocks on each of 256 CUs
-constexpr int CT_MIN_SLICE = 64;             // structures of a slice at least: a slice ends in up to 2 atomics per pair
-
-__device__ __forceinline__ int ct_atom(const int* __restrict__ sel, int k, int n) {
-  const int a = sel[k];
-  return (a >= 0 && a < n) ? a : 0;
-}
 
 __global__ __launch_bounds__(256) void contact_prep_k(const float* __restrict__ xyz, const int* __restrict__ sel, int S, int n, int m,
                                                       float4* __restrict__ packed, double* __restrict__ rg2,
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(256) void contact_prep_k(const float* __restrict__ 
   double sx = 0.0, sy = 0.0, sz = 0.0;
   bool ok = true;
   for (int k = lane; k < m; k += 64) {
-    const f3 p = ld3(base + 3 * (size_t)ct_atom(sel, k, n));
+    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
     ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     row[k] = make_float4(p.x, p.y, p.z, 0.f);
     sx += (double)p.x, sy += (double)p.y, sz += (double)p.z;
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
                                                        float cutoff2, int* __restrict__ counts, int* __restrict__ n_contacts,
                                                        int* __restrict__ n_native) {
   __shared__ float4 st[CT_CHUNK][CT_ROWS + CT_COLS];
-  __shared__ int hits[2][CT_CHUNK];
+  __shared__ ChunkHits<CT_CHUNK> hits;
   const int r0 = (int)blockIdx.y * CT_ROWS, c0 = (int)blockIdx.x * CT_COLS;
   if (c0 + CT_COLS - 1 <= r0) return;                        // no column of the tile is above a row of it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -115,7 +108,7 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
       if (s0 + sl < s_end && at < m) v = packed[(size_t)(s0 + sl) * m + at];
       st[sl][a] = v;
     }
-    if (tid < 2 * CT_CHUNK) hits[tid / CT_CHUNK][tid % CT_CHUNK] = 0;
+    hits.zero(tid);
     __syncthreads();
     if (wave_live) {
 #pragma unroll 1
@@ -131,16 +124,13 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
         }
         hit &= ok;
         if (hit != 0) {
-          atomicAdd(&hits[0][sl], __popc(hit));
-          if ((hit & nat) != 0) atomicAdd(&hits[1][sl], __popc(hit & nat));
+          hits.add(0, sl, __popc(hit));
+          if ((hit & nat) != 0) hits.add(1, sl, __popc(hit & nat));
         }
       }
     }
     __syncthreads();
-    if (tid < 2 * CT_CHUNK) {
-      const int which = tid / CT_CHUNK, sl = tid % CT_CHUNK, v = hits[which][sl];
-      if (v != 0 && s0 + sl < s_end) atomicAdd((which ? n_native : n_contacts) + s0 + sl, v);
-    }
+    hits.flush(s0, s_end, tid, n_contacts, n_native);
   }
 #pragma unroll
   for (int u = 0; u < 32; ++u) {
@@ -201,18 +191,6 @@ __global__ __launch_bounds__(64) void contact_groups_k(const float4* __restrict_
   }
 }
 
-// how many slices the structure axis is cut into for `tiles` independent pieces of work, and the structures of a slice
-static inline int ct_slices(int S, int tiles, int quantum, int* per) {
-  int want = (CT_TARGET_BLOCKS + tiles - 1) / tiles;
-  const int most = (S + CT_MIN_SLICE - 1) / CT_MIN_SLICE;
-  if (want > most) want = most;
-  if (want < 1) want = 1;
-  int p = (S + want - 1) / want;
-  p = (p + quantum - 1) / quantum * quantum;
-  *per = p;
-  return (S + p - 1) / p;
-}
-
 static int ct_check(const void* xyz, const void* sel, const void* excl, int S, int n_atoms, int m, float cutoff2,
                     const void* n_contacts, const void* n_native, const void* bad, const void* workspace, size_t workspace_bytes,
                     const char** why) {
@@ -260,7 +238,7 @@ int cgv_contact_counts(const float* xyz, const int32_t* sel, const uint32_t* exc
   int live = 0;                                              // tiles that hold a pair i < j
   for (int r = 0; r < nr; ++r) live += nc - (r >> 1);
   int per;
-  const int slices = cgv::ct_slices(n_structures, live, cgv::CT_CHUNK, &per);
+  const int slices = cgv::struct_slices(n_structures, live, cgv::CT_CHUNK, &per);
   hipLaunchKernelGGL(cgv::contact_pairs_k, dim3((unsigned)nc, (unsigned)nr, (unsigned)slices), dim3(256), 0, st, packed, excluded,
                      native, n_structures, m, (m + 31) / 32, per, cutoff2, counts, n_contacts, n_native);
   return cgv::check_launch("cgv_contact_counts");
@@ -285,7 +263,7 @@ int cgv_contact_group_counts(const float* xyz, const int32_t* sel, const int32_t
   if (rc || n_groups < 2) return rc;
   const long long pairs = (long long)n_groups * (n_groups - 1) / 2;
   int per;
-  const int slices = cgv::ct_slices(n_structures, pairs > cgv::CT_TARGET_BLOCKS ? cgv::CT_TARGET_BLOCKS : (int)pairs, 64, &per);
+  const int slices = cgv::struct_slices(n_structures, pairs > cgv::PACKED_TARGET_BLOCKS ? cgv::PACKED_TARGET_BLOCKS : (int)pairs, 64, &per);
   hipLaunchKernelGGL(cgv::contact_groups_k, dim3((unsigned)n_groups, (unsigned)n_groups, (unsigned)slices), dim3(64), 0, st, packed,
                      group_start, excluded, native, n_structures, m, (m + 31) / 32, n_groups, (n_groups + 31) / 32, per, cutoff2,
                      group_counts, n_contacts, n_native);

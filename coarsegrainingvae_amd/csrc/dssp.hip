@@ -148,8 +148,6 @@ __device__ __forceinline__ bool ds_accepts(const DsSlot& L, int i, int j) {
   return e < -0.5f;
 }
 
-__device__ __forceinline__ int ds_atom(int a, int n) { return (a >= 0 && a < n) ? a : 0; }
-
 // GROUP threads a structure: 64 (a wave; the block walks the structures, class_counts gathered in LDS) or 256 (the block)
 template <int GROUP>
 __global__ __launch_bounds__(DS_THREADS) void dssp_k(const float* __restrict__ xyz, const int* __restrict__ res,
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(DS_THREADS) void dssp_k(const float* __restrict__ x
     for (int r = t; r < R; r += GROUP) {
       bool ok = true;
       for (int a = 0; a < 4; ++a) {
-        const f3 p = ld3(base + 3 * (size_t)ds_atom(res[4 * r + a], n));
+        const f3 p = ld3(base + 3 * (size_t)sel_atom(res[4 * r + a], n));
         ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
         float* q = L.pos + 3 * (a * R + r);
         q[0] = p.x, q[1] = p.y, q[2] = p.z;
@@ -185,7 +183,7 @@ __global__ __launch_bounds__(DS_THREADS) void dssp_k(const float* __restrict__ x
       const bool has = pc >= 0 && po >= 0;
       float hx = 0.f, hy = 0.f, hz = 0.f;
       if (has) {
-        const f3 c = ld3(base + 3 * (size_t)ds_atom(pc, n)), o = ld3(base + 3 * (size_t)ds_atom(po, n));
+        const f3 c = ld3(base + 3 * (size_t)sel_atom(pc, n)), o = ld3(base + 3 * (size_t)sel_atom(po, n));
         ok = ok && isfinite(c.x) && isfinite(c.y) && isfinite(c.z) && isfinite(o.x) && isfinite(o.y) && isfinite(o.z);
         const float wx = __fsub_rn(c.x, o.x), wy = __fsub_rn(c.y, o.y), wz = __fsub_rn(c.z, o.z);
         const float l = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(wx, wx), __fmul_rn(wy, wy)), __fmul_rn(wz, wz)));

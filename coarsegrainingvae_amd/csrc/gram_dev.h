@@ -13,6 +13,7 @@
 // own part is what a feature is and how many products it carries.
 #pragma once
 #include "cgv_common.h"
+#include "sq_dist.h"
 
 namespace cgv {
 
@@ -147,19 +148,10 @@ struct GramHist {                             // two of the components binned in
   int* outside;
 };
 
-// lane 0 holds the sum.  A fixed tree: the same bits on every run.  An xor tree (every lane holds the sum) gives lane 0
-// the same bits: at step w lane 0 adds lane w's value, and in both trees lane w's value was formed at the steps w' > w from
-// lanes w + w' <= 63 (in range, and w ^ w' = w + w') in the same pairing.
-__device__ __forceinline__ double gram_wave_sum(double v) {
-#pragma unroll
-  for (int w = 32; w >= 1; w >>= 1) v += __shfl_down(v, w);
-  return v;
-}
-
 // out [S,K] = (feature - mean) W, one wave per structure.  `Feature` says what a structure's features are:
 //   bool good(int s)             (uniform over the wave) false: the structure's components are NaN and it counts in `outside`
 //   double value(int s, int f)   feature f < d of a good structure s, the mean not yet subtracted
-// Each lane sums its strided share of the features in ascending order, gram_wave_sum combines the lanes; lane 0 writes the
+// Each lane sums its strided share of the features in ascending order, sq_wave_sum combines the lanes; lane 0 writes the
 // components and bins two of them into the block's LDS histogram (integer atomics), flushed with one integer vector atomic
 // per non-zero slot.  The bin rule: for lo <= v < hi in fp64 the bin is floor((v - lo) * nb / (hi - lo)), clamped to [0, nb)
 // against rounding alone; a structure with either component outside its range or NaN counts once in `outside`.
@@ -190,7 +182,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void gram_project_k(const Feature fea
     double va = 0.0, vb = 0.0;
 #pragma unroll
     for (int c = 0; c < K; ++c) {
-      double v = gram_wave_sum(acc[c]);
+      double v = sq_wave_sum(acc[c]);
       if (!good) v = (double)NAN;
       if (out && lane == 0) out[(size_t)s * K + c] = v;
       if (c == h.ca) va = v;

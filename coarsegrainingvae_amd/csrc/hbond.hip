@@ -30,7 +30,7 @@
 // same bits, and nothing depends on how the caller cuts the structures into launches.
 #include <math.h>
 
-#include "cgv_common.h"
+#include "packed_dev.h"
 #include "sq_dist.h"
 
 namespace cgv {
@@ -44,13 +44,6 @@ constexpr int HB_STAGE = 2 * HB_ROWS + HB_COLS;   // float4 of a staged structur
 constexpr int HB_MAX_HYDROGENS = 4096;
 constexpr int HB_MAX_ACCEPTORS = 4096;
 constexpr int HB_MAX_STRUCTURES = 1 << 20;   // per launch
-constexpr int HB_TARGET_BLOCKS = 1024;       // 4 blocks on each of 256 CUs
-constexpr int HB_MIN_SLICE = 64;             // structures of a slice at least: a slice ends in an atomic per bonded pair
-
-__device__ __forceinline__ int hb_atom(const int* __restrict__ table, int k, int n) {
-  const int a = table[k];
-  return (a >= 0 && a < n) ? a : 0;
-}
 
 __global__ __launch_bounds__(256) void hbond_prep_k(const float* __restrict__ xyz, const int* __restrict__ don_h,
                                                     const int* __restrict__ don_d, const int* __restrict__ acc, int S, int n,
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(256) void hbond_prep_k(const float* __restrict__ xy
   float4* row = packed + (size_t)s * P;
   bool ok = true;
   for (int k = lane; k < P; k += 64) {
-    const int at = k < nH ? hb_atom(don_h, k, n) : k < 2 * nH ? hb_atom(don_d, k - nH, n) : hb_atom(acc, k - 2 * nH, n);
+    const int at = sel_atom(k < nH ? don_h[k] : k < 2 * nH ? don_d[k - nH] : acc[k - 2 * nH], n);
     const f3 p = ld3(base + 3 * (size_t)at);
     ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     row[k] = make_float4(p.x, p.y, p.z, 0.f);
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(256) void hbond_pairs_k(const float4* __restrict__ 
                                                      unsigned long long* __restrict__ pair_counts, int* __restrict__ n_hbonds,
                                                      int* __restrict__ n_native, unsigned long long* __restrict__ bits) {
   __shared__ float4 st[HB_CHUNK][HB_STAGE];
-  __shared__ int hits[2][HB_CHUNK];
+  __shared__ ChunkHits<HB_CHUNK> hits;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int word = (int)blockIdx.x, r0 = (int)blockIdx.y * HB_ROWS, c0 = word * HB_COLS;
   const int P = 2 * nH + nA, rw = r0 + HB_RPW * wave;        // the first of this wave's rows
@@ -116,7 +109,7 @@ __global__ __launch_bounds__(256) void hbond_pairs_k(const float4* __restrict__ 
       if (s0 + sl < s_end && at >= 0) v = packed[(size_t)(s0 + sl) * P + at];
       st[sl][a] = v;
     }
-    if (tid < 2 * HB_CHUNK) hits[tid / HB_CHUNK][tid % HB_CHUNK] = 0;
+    hits.zero(tid);
     __syncthreads();
 #pragma unroll 1
     for (int sl = 0; sl < HB_CHUNK; ++sl) {
@@ -138,33 +131,18 @@ __global__ __launch_bounds__(256) void hbond_pairs_k(const float4* __restrict__ 
         if (bits != nullptr && lane == 0 && rw + u < nH) bits[((size_t)(s0 + sl) * nH + (rw + u)) * words + word] = w;
       }
       if (lane == 0) {
-        if (nh != 0) atomicAdd(&hits[0][sl], nh);
-        if (nn != 0) atomicAdd(&hits[1][sl], nn);
+        if (nh != 0) hits.add(0, sl, nh);
+        if (nn != 0) hits.add(1, sl, nn);
       }
     }
     __syncthreads();
-    if (tid < 2 * HB_CHUNK) {
-      const int which = tid / HB_CHUNK, sl = tid % HB_CHUNK, v = hits[which][sl];
-      if (v != 0 && s0 + sl < s_end) atomicAdd((which ? n_native : n_hbonds) + s0 + sl, v);
-    }
+    hits.flush(s0, s_end, tid, n_hbonds, n_native);
   }
   if (c0 + lane < nA) {
 #pragma unroll
     for (int u = 0; u < HB_RPW; ++u)
       if (cnt[u] != 0) atomicAdd(pair_counts + (size_t)(rw + u) * nA + c0 + lane, (unsigned long long)cnt[u]);   // cnt != 0: rw + u < nH
   }
-}
-
-// how many slices the structure axis is cut into for `tiles` tiles of the table, and the structures of a slice
-static inline int hb_slices(int S, int tiles, int* per) {
-  int want = (HB_TARGET_BLOCKS + tiles - 1) / tiles;
-  const int most = (S + HB_MIN_SLICE - 1) / HB_MIN_SLICE;
-  if (want > most) want = most;
-  if (want < 1) want = 1;
-  int p = (S + want - 1) / want;
-  p = (p + HB_CHUNK - 1) / HB_CHUNK * HB_CHUNK;
-  *per = p;
-  return (S + p - 1) / p;
 }
 
 static inline size_t hb_workspace(int S, int nH, int nA) { return (size_t)S * (size_t)(2 * nH + nA) * sizeof(float4); }
@@ -210,7 +188,7 @@ int cgv_hbond_counts(const float* xyz, const int32_t* don_h, const int32_t* don_
   if (rc) return rc;
   const int words = (nA + 63) / 64, tiles = (nH + cgv::HB_ROWS - 1) / cgv::HB_ROWS;
   int per;
-  const int slices = cgv::hb_slices(S, words * tiles, &per);
+  const int slices = cgv::struct_slices(S, words * tiles, cgv::HB_CHUNK, &per);
   hipLaunchKernelGGL(cgv::hbond_pairs_k, dim3((unsigned)words, (unsigned)tiles, (unsigned)slices), dim3(256), 0, st, packed,
                      (const unsigned long long*)excluded, (const unsigned long long*)native, S, nH, nA, words, per, cutoff2, c2,
                      (unsigned long long*)pair_counts, n_hbonds, n_native, (unsigned long long*)bits);

@@ -1,0 +1,41 @@
+// What the pair kernels that stream a packed copy [S, P] float4 of every structure share (K20 contact_map.hip, K25
+// hbond.hip): the rule that cuts the structure axis into slices, and the per-structure counters of the chunk of structures a
+// block stages at a time.  Only integers here, but EVERY FILE THAT INCLUDES THIS IS COMPILED WITH -ffp-contract=off
+// (build.py: SOURCE_FLAGS): the predicates beside it are restated on the host bit for bit.
+#pragma once
+#include "cgv_common.h"
+
+namespace cgv {
+
+constexpr int PACKED_TARGET_BLOCKS = 1024;   // 4 blocks on each of 256 CUs
+constexpr int PACKED_MIN_SLICE = 64;         // structures of a slice at least: a slice ends in an atomic or two per counted pair
+
+// how many slices the structure axis is cut into for `tiles` independent pieces of work, and the structures of a slice (a
+// multiple of `quantum`, the structures a block takes at a time)
+static inline int struct_slices(int S, int tiles, int quantum, int* per) {
+  int want = (PACKED_TARGET_BLOCKS + tiles - 1) / tiles;
+  const int most = (S + PACKED_MIN_SLICE - 1) / PACKED_MIN_SLICE;
+  if (want > most) want = most;
+  if (want < 1) want = 1;
+  int p = (S + want - 1) / want;
+  p = (p + quantum - 1) / quantum * quantum;
+  *per = p;
+  return (S + p - 1) / p;
+}
+
+// The LDS counters of a pair kernel for the CHUNK structures s0 .. s0 + CHUNK - 1 it has staged: per structure the pairs that
+// count and the native ones among them.  zero() between the chunk loop's two barriers, add() from the pair loop
+template <int CHUNK>
+struct ChunkHits {
+  int hits[2][CHUNK];
+  __device__ __forceinline__ void zero(int tid) { if (tid < 2 * CHUNK) hits[tid / CHUNK][tid % CHUNK] = 0; }
+  __device__ __forceinline__ void add(int which, int sl, int v) { atomicAdd(&hits[which][sl], v); }
+  __device__ __forceinline__ void flush(int s0, int s_end, int tid, int* __restrict__ n_all, int* __restrict__ n_native) {
+    if (tid < 2 * CHUNK) {
+      const int which = tid / CHUNK, sl = tid % CHUNK, v = hits[which][sl];
+      if (v != 0 && s0 + sl < s_end) atomicAdd((which ? n_native : n_all) + s0 + sl, v);
+    }
+  }
+};
+
+}  // namespace cgv

@@ -34,7 +34,7 @@ __host__ __device__ inline size_t pm_slice(int d) { return gram_slice(d, 1, 1, 1
 // where feature `feat` (< d) of a structure lies: 3 * atom + component, the atom validated
 __device__ __forceinline__ size_t pca_offset(const int* __restrict__ sel, int feat, int n) {
   const int a = feat / 3, c = feat - 3 * a, v = sel[a];
-  return 3 * (size_t)((v >= 0 && v < n) ? v : 0) + (size_t)c;
+  return 3 * (size_t)sel_atom(v, n) + (size_t)c;
 }
 
 // grid: x = upper tile pair, y = structure range

@@ -71,8 +71,7 @@ __global__ __launch_bounds__(256) void sasa_prep_k(const float* __restrict__ xyz
   float4* row = packed + (size_t)s * m;
   bool ok = true, near = true;
   for (int k = lane; k < m; k += 64) {
-    const int a = sel[k];
-    const f3 p = ld3(base + 3 * (size_t)((a >= 0 && a < n) ? a : 0));
+    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
     const float rk = r[k];
     ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     near = near && fabsf(p.x) <= SA_FILTER_MAX_COORD && fabsf(p.y) <= SA_FILTER_MAX_COORD && fabsf(p.z) <= SA_FILTER_MAX_COORD;

@@ -1,5 +1,14 @@
-// The bond test shared by the sample-quality kernels (K12 sample_quality.hip, K14 ensemble_check.hip): tile size, class
-// limit, the bit-reproducible squared distance and the fixed-tree wave sums.
+// The bit-reproducible squared distance and the fixed-tree wave sums of every kernel whose integers or fp64 sums the host
+// restates bit for bit, and the tile size and class limit of the sample-quality kernels' bond test.  Who includes it, and why
+// each of them has its entry in build.py's SOURCE_FLAGS:
+//   K12 sample_quality.hip, K14 ensemble_check.hip   sq_dist2 against host-derived bond thresholds; the wave sums
+//   K16 tica.hip                                     a feature is sqrtf(sq_dist2), restated in numpy.float32
+//   K20 contact_map.hip                              sq_dist2 < cutoff2; rg2 through sq_wave_sum(double)
+//   K23 sasa.hip                                     sq_dist2 of a rounded sphere point against a rounded r * r
+//   K25 hbond.hip                                    sq_dist2 against a cutoff, and a rounded dot product beside it
+//   K26 dssp.hip                                     sq_dist2 beside its rounded reciprocal distances
+//   K27 pca.hip (through gram_dev.h)                 sq_wave_sum(double) alone; its own fp64 feature needs the flag as well
+// packed_dev.h and gram_dev.h stand on the same contract.
 #pragma once
 #include "cgv_common.h"
 
@@ -24,9 +33,12 @@ __device__ __forceinline__ int sq_wave_sum(int v) {
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
   return v;                                 // lane 0 holds the sum
 }
+// lane 0 holds the sum.  A fixed tree: the same bits on every run.  An xor tree (every lane holds the sum) gives lane 0
+// the same bits: at step d lane 0 adds lane d's value, and in both trees lane d's value was formed at the steps d' > d from
+// lanes d + d' <= 63 (in range, and d ^ d' = d + d') in the same pairing.
 __device__ __forceinline__ double sq_wave_sum(double v) {
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);   // fixed tree: the same bits on every run
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
   return v;
 }
 

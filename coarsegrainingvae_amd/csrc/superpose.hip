@@ -67,11 +67,6 @@ static inline SpLayout sp_layout(int sa, int sb) {
   return L;
 }
 
-__device__ __forceinline__ int sp_atom(const int* __restrict__ sel, int k, int n) {
-  const int a = sel[k];
-  return (a >= 0 && a < n) ? a : 0;
-}
-
 __global__ __launch_bounds__(256) void superpose_prep_k(const float* __restrict__ xyz, const int* __restrict__ sel, int S, int n,
                                                         int m, double* __restrict__ cen, double* __restrict__ G,
                                                         int* __restrict__ bad) {
@@ -81,13 +76,13 @@ __global__ __launch_bounds__(256) void superpose_prep_k(const float* __restrict_
   double sx = 0.0, sy = 0.0, sz = 0.0;
   bool ok = true;
   for (int k = 0; k < m; ++k) {
-    const f3 p = ld3(base + 3 * (size_t)sp_atom(sel, k, n));
+    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
     ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
     sx += (double)p.x, sy += (double)p.y, sz += (double)p.z;
   }
   double cx = sx / (double)m, cy = sy / (double)m, cz = sz / (double)m, g = 0.0;
   for (int k = 0; k < m; ++k) {
-    const f3 p = ld3(base + 3 * (size_t)sp_atom(sel, k, n));
+    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
     const double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;
     g += (dx * dx + dy * dy) + dz * dz;
   }
@@ -132,7 +127,7 @@ __global__ __launch_bounds__(SP_THREADS) void superpose_cross_k(
   for (int k0 = 0; k0 < m; k0 += SP_KA) {
     __syncthreads();                                         // the previous stage has been read
     const bool in = k0 + kk < m;
-    const int at = in ? sp_atom(sel, k0 + kk, n) : 0;
+    const int at = in ? sel_atom(sel[k0 + kk], n) : 0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       double x = 0.0, y = 0.0, z = 0.0;

@@ -53,8 +53,7 @@ __global__ __launch_bounds__(GRAM_THREADS) void tica_moments_k(const float* __re
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
     const int vi = live_i ? pairs[2 * (size_t)fi + a] : 0, vj = live_j ? pairs[2 * (size_t)fj + a] : 0;
-    ai[a] = (vi >= 0 && vi < n) ? vi : 0;
-    aj[a] = (vj >= 0 && vj < n) ? vj : 0;
+    ai[a] = sel_atom(vi, n), aj[a] = sel_atom(vj, n);
   }
   const int t_begin = (int)blockIdx.y * per_range;           // t_begin < N (the host's grid)
   const int t_end = min(N, t_begin + per_range);
@@ -108,7 +107,7 @@ struct TicaFeature {
   __device__ bool good(int) const { return true; }
   __device__ double value(int s, int f) const {
     const int a = pairs[2 * (size_t)f], b = pairs[2 * (size_t)f + 1];
-    return tica_feature(xyz + 3 * (size_t)n * (size_t)s, (a >= 0 && a < n) ? a : 0, (b >= 0 && b < n) ? b : 0);
+    return tica_feature(xyz + 3 * (size_t)n * (size_t)s, sel_atom(a, n), sel_atom(b, n));
   }
 };
 
