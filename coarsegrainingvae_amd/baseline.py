@@ -31,8 +31,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, options
+from . import _lib
 from . import primitives as prim
+from .steploop import check_order, check_steps, chunks, forced_form, steps_per_epoch
 
 LINEAR, EQUILINEAR = 1, 2                 # include/cgvae_hip.h: CGV_BASELINE_LINEAR / _EQUILINEAR
 RESIDENT, GLOBAL = 1, 2                   # CGV_BASELINE_RESIDENT / _GLOBAL
@@ -49,10 +50,8 @@ def feature_count(kind: int, n_cgs: int, knn: int) -> int:
 def choose_form(kind: int, n_atoms: int, C: int, batch_size: int) -> int:
     """The one rule: matrix, moments and the batch's features in one workgroup's LDS when they fit
     (cgv_baseline_resident_fits), the same loop on global memory otherwise.  options ``baseline_form`` = 1 / 2 forces a form."""
-    forced = options.get("baseline_form")
-    if forced in (RESIDENT, GLOBAL):
-        return forced
-    return RESIDENT if _lib.load().cgv_baseline_resident_fits(int(kind), int(n_atoms), int(C), int(batch_size)) else GLOBAL
+    return forced_form("baseline_form", lambda: RESIDENT if _lib.load().cgv_baseline_resident_fits(
+        int(kind), int(n_atoms), int(C), int(batch_size)) else GLOBAL)
 
 
 class FixedPool(nn.Module):
@@ -128,13 +127,7 @@ def _cached(model, slot, source, extra, build):
 def _order_on(model, order, n_frames, dev):
     """(int32 [epochs * n_train] on the device, n_train) of a frame order table, validated once per table."""
     def build():
-        table = order.detach().cpu().numpy() if torch.is_tensor(order) else np.asarray(order)
-        if table.ndim != 2 or table.shape[1] == 0:
-            raise ValueError("order must be [epochs, n_train]")
-        if not np.issubdtype(table.dtype, np.integer):
-            raise TypeError(f"the frame order table must hold integers, not {table.dtype}")
-        if table.min() < 0 or table.max() >= n_frames:
-            raise ValueError("frame order table points outside the frames")
+        table = check_order(order.detach().cpu().numpy() if torch.is_tensor(order) else np.asarray(order), n_frames)
         return torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32).reshape(-1)).to(dev), int(table.shape[1])
     if torch.is_tensor(order) and order.is_cuda and order.dtype == torch.int32 and order.dim() == 2 and order.shape[1] > 0:
         return order.reshape(-1).contiguous(), int(order.shape[1])        # the caller's own device table (the kernel clamps)
@@ -183,9 +176,7 @@ class _LinearKind(nn.Module):
         if mode == TRAIN and steps > 0 and first_step != self.adam_steps:
             raise ValueError(f"training from schedule position {first_step}, but the model's Adam state stands at step "
                              f"{self.adam_steps}: continue there, or reset_optimizer() first")
-        spe = -(-n_train // batch)
-        if steps < 0 or first_step < 0 or first_step + steps > (order_dev.numel() // n_train) * spe:
-            raise ValueError("more steps than the frame order table holds")
+        check_steps(first_step, steps, order_dev.numel() // n_train, n_train, batch)
         form = choose_form(self.kind, self.n_atoms, self.C, batch) if form is None else int(form)
         edges_dev, E = _cached(self, "edges", edges, str(dev), lambda: _edges_on(edges, dev))
         lib = _lib.load()
@@ -203,9 +194,7 @@ class _LinearKind(nn.Module):
         log = torch.zeros(max(steps, 1), 2, device=dev)
         out = torch.zeros(batch * self.n_atoms * 3 + self.B.numel(), device=dev) if probe else None
         with torch.cuda.device(dev):
-            start = 0
-            while start < steps:
-                cnt = min(CHUNK_STEPS, steps - start)
+            for start, cnt in chunks(steps, CHUNK_STEPS):
                 step0 = first_step + start
                 # Adam's step count is the schedule position (checked above against the model's own count)
                 _lib.call("cgv_baseline_steps", self.kind, form, int(mode), _lib.ptr(self.B.data), _lib.ptr(m), _lib.ptr(v),
@@ -214,7 +203,6 @@ class _LinearKind(nn.Module):
                           float(gamma), float(lr), BETAS[0], BETAS[1], EPS, _lib.ptr(log[start:]),
                           _lib.ptr(out) if probe and start + cnt == steps else None, _lib.ptr(self._ws), self._ws.numel(),
                           _lib.stream_ptr())
-                start += cnt
         if mode == TRAIN and steps > 0:
             self.adam_steps = first_step + steps
         return log[:steps], out
@@ -355,15 +343,6 @@ class MLP(nn.Module):
         return xyz, self.decode(self.pooler.cg_xyz(xyz))
 
 
-def _order_table(order, n_frames):
-    order = np.ascontiguousarray(order, dtype=np.int64)
-    if order.ndim != 2 or order.shape[1] == 0:
-        raise ValueError("order must be [epochs, n_train]")
-    if order.min() < 0 or order.max() >= n_frames:
-        raise ValueError("frame order table points outside the frames")
-    return order
-
-
 def fit(model, frames, order, batch_size, lr, gamma, edges=None, first_step=0, steps=None, train=True, form=None):
     """Steps ``first_step .. first_step + steps`` (default: to the end) of the schedule ``order`` -- int [epochs, n_train]
     frame indices, ``batch_size`` consecutive entries of a row per step, the last batch of a row the partial one -- on
@@ -380,7 +359,7 @@ def fit(model, frames, order, batch_size, lr, gamma, edges=None, first_step=0, s
     if order.ndim != 2 or order.shape[1] == 0:
         raise ValueError("order must be [epochs, n_train]")
     n_train = int(order.shape[1])
-    spe = -(-n_train // batch_size)
+    spe = steps_per_epoch(n_train, batch_size)
     total = int(order.shape[0]) * spe
     steps = total - first_step if steps is None else int(steps)
     if isinstance(model, _LinearKind):
@@ -395,7 +374,7 @@ def fit(model, frames, order, batch_size, lr, gamma, edges=None, first_step=0, s
     dev = model.mlp[0].weight.device
     frames = torch.as_tensor(frames, dtype=torch.float32).to(dev)
     table = _cached(model, "order", order, (int(frames.shape[0]), str(dev)), lambda: torch.from_numpy(
-        _order_table(order.cpu().numpy() if torch.is_tensor(order) else order, frames.shape[0])).to(dev))
+        check_order(np.ascontiguousarray(order.cpu().numpy() if torch.is_tensor(order) else order, dtype=np.int64), frames.shape[0])).to(dev))
     loss_fn = _cached(model, "loss", edges, (float(gamma), str(dev)), lambda: ReconLoss(edges, gamma, dev))
     if train:
         if model.optimizer is None:

@@ -20,7 +20,8 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, options
+from . import _lib
+from .steploop import check_order, check_steps, chunks, forced_form, steps_per_epoch
 
 RESIDENT, STREAMED = 1, 2                 # include/cgvae_hip.h: CGV_CGAE_RESIDENT / CGV_CGAE_STREAMED
 FORM_NAMES = {RESIDENT: "resident", STREAMED: "streamed"}
@@ -48,17 +49,10 @@ def frame_order(n_train: int, batch_size: int, n_epochs: int, seed: int) -> np.n
     return rng.permuted(np.tile(np.arange(n_train, dtype=np.int32), (n_epochs, 1)), axis=1)
 
 
-def steps_per_epoch(n_train: int, batch_size: int) -> int:
-    return -(-n_train // batch_size)
-
-
 def choose_form(n_atoms: int, n_cgs: int, batch_size: int) -> int:
     """The one rule: everything in one workgroup's LDS when n_atoms * n_cgs (and the batch's bead coordinates) fit it
     (cgv_cgae_resident_fits), the multi-block form otherwise.  options ``cgae_form`` = 1 / 2 forces a form."""
-    forced = options.get("cgae_form")
-    if forced in (RESIDENT, STREAMED):
-        return forced
-    return RESIDENT if _lib.load().cgv_cgae_resident_fits(n_atoms, n_cgs, batch_size) else STREAMED
+    return forced_form("cgae_form", lambda: RESIDENT if _lib.load().cgv_cgae_resident_fits(n_atoms, n_cgs, batch_size) else STREAMED)
 
 
 class Learner:
@@ -70,10 +64,8 @@ class Learner:
         self.n_frames, self.n, _ = frames.shape
         self.K = int(W.shape[1])
         assert tuple(W.shape) == (self.n, self.K) and tuple(D.shape) == (self.K, self.n)
-        order = np.ascontiguousarray(order, dtype=np.int32)
+        order = check_order(np.ascontiguousarray(order, dtype=np.int32), self.n_frames)
         self.n_train, self.batch = int(order.shape[1]), int(batch_size)
-        if order.min() < 0 or order.max() >= self.n_frames:
-            raise ValueError("frame order table points outside the frames")
         self.total_steps = int(order.shape[0]) * steps_per_epoch(self.n_train, self.batch)
         self.form = choose_form(self.n, self.K, self.batch) if form is None else int(form)
         frames = frames - frames.mean(1, keepdim=True)                    # datasets.py:222-223, once
@@ -90,30 +82,24 @@ class Learner:
         """``steps`` more optimiser steps (default: the rest of the schedule).  ``noise`` [steps, n, K]: explicit Gumbel noise
         instead of the generator's.  ``probe``: returns M, dW, dD, cg_xyz of the last step."""
         steps = self.total_steps - self.done if steps is None else int(steps)
-        if steps < 0 or self.done + steps > self.total_steps:
-            raise ValueError("more steps than the frame order table holds")
+        check_steps(self.done, steps, self.order.numel() // self.n_train, self.n_train, self.batch)
         if noise is not None:
             noise = noise.to(self.W.device, torch.float32).contiguous()
             assert tuple(noise.shape) == (steps, self.n, self.K)
         nk = self.n * self.K
         out = torch.zeros(3 * nk + self.batch * self.K * 3, device=self.W.device) if probe else None
         with torch.cuda.device(self.W.device):
-            start = 0
-            while start < steps:
-                cnt = min(CHUNK_STEPS, steps - start)
+            for start, cnt in chunks(steps, CHUNK_STEPS):
                 _lib.call("cgv_cgae_steps", self.form, _lib.ptr(self.W), _lib.ptr(self.D), *(_lib.ptr(m) for m in self.moments),
                           _lib.ptr(self.frames), self.n_frames, _lib.ptr(self.order), self.order.numel(), self.n_train,
                           self.batch, self.n, self.K, self.done, cnt, self.reg_weight, self.lr, 0.9, 0.999, 1e-8, self.seed,
                           _lib.ptr(noise[start:]) if noise is not None else None, _lib.ptr(self.loss_log[self.done:]),
                           _lib.ptr(out) if probe and start + cnt == steps else None,
                           _lib.ptr(self.workspace), self.workspace.numel(), _lib.stream_ptr())
-                start += cnt
                 self.done += cnt
         if not probe:
             return None
-        last = self.done - 1
-        spe = steps_per_epoch(self.n_train, self.batch)
-        cnt = min(self.batch, self.n_train - (last % spe) * self.batch)
+        cnt = min(self.batch, self.n_train - ((self.done - 1) % steps_per_epoch(self.n_train, self.batch)) * self.batch)
         return {"M": out[:nk].view(self.n, self.K), "dW": out[nk:2 * nk].view(self.n, self.K),
                 "dD": out[2 * nk:3 * nk].view(self.K, self.n), "cg_xyz": out[3 * nk:].view(self.batch, self.K, 3)[:cnt]}
 
@@ -191,10 +177,7 @@ def bond_csr(bonds, n_atoms: int):
 def choose_newman_form(n_atoms: int, n_edges: int) -> int:
     """Per-source state in the workgroup's LDS when it fits (cgv_newman_resident_fits), in the workspace otherwise.
     options ``newman_form`` = 1 / 2 forces a form."""
-    forced = options.get("newman_form")
-    if forced in (RESIDENT, STREAMED):
-        return forced
-    return RESIDENT if _lib.load().cgv_newman_resident_fits(int(n_atoms), int(n_edges)) else STREAMED
+    return forced_form("newman_form", lambda: RESIDENT if _lib.load().cgv_newman_resident_fits(int(n_atoms), int(n_edges)) else STREAMED)
 
 
 class _NewmanGraph:

@@ -34,16 +34,16 @@
 //   global    the same loop on the caller's P / moments in place and the small arrays in the workspace
 // recon, G ([b,n,3] each) and w ([b,E]), doubles, live in the workspace in both forms.  Same template, same arithmetic (this file is
 // compiled without fp contraction, every fused multiply-add is written out): the two forms give the same bits.
+// The schedule rule, Adam, the loss partials and the host checks are steploop_dev.h's, shared with K13.
 #include <algorithm>
 
-#include "cgv_common.h"
+#include "steploop_dev.h"
 
 namespace cgv {
 namespace baseline {
 
-constexpr int NT = 512;
-constexpr int NW = NT / WAVE;
-constexpr size_t LDS_LIMIT = 160 * 1024;  // one workgroup may hold all of a CU's LDS
+using namespace steploop;                 // NT, NW, LDS_LIMIT, Step, step_of, Adam, wave_partial, the host checks
+
 constexpr int LOSS_NT = 256;
 constexpr long long CAP = 1ll << 24;      // n C, batch n, batch C, batch E and 2 E stay below this (header)
 
@@ -64,25 +64,8 @@ struct Params {
   double lr, beta1, beta2, eps;
 };
 
-struct Step {
-  long long step;                        // index in the whole schedule (Adam's step count is step + 1)
-  int local, off, cnt, last;
-};
-
-__host__ __device__ inline Step step_of(int n_train, int batch, long long step, int local, int last) {
-  const int spe = (n_train + batch - 1) / batch;
-  const long long epoch = step / spe;
-  const int si = (int)(step % spe);
-  Step st;
-  st.step = step; st.local = local; st.last = last;
-  st.off = (int)(epoch * n_train) + si * batch;
-  st.cnt = min(batch, n_train - si * batch);                       // the last, partial batch of an epoch is kept
-  return st;
-}
-
 __device__ __forceinline__ const float* frame_of(const Params& P, const Step& st, int b) {
-  const int f = min(max(P.order[st.off + b], 0), P.n_frames - 1);   // a bad table entry must not become a wild read
-  return P.frames + (size_t)f * P.n * 3;
+  return steploop::frame_of(P.frames, P.order, P.n_frames, P.n, st, b);
 }
 __device__ __forceinline__ int bead_of(const Params& P, int a) { return min(max(P.map[a], 0), P.K - 1); }
 __device__ __forceinline__ int atom_of(int i, int n) { return min(max(i, 0), n - 1); }
@@ -182,12 +165,6 @@ __device__ __forceinline__ void ph_bead_mean(const Params& P, int tid, const Ste
   }
 }
 
-__device__ __forceinline__ void wave_partial(const Params& P, int tid, double a, int slot) {
-#pragma unroll
-  for (int o = WAVE / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, WAVE);   // fixed tree inside the wave
-  if ((tid & (WAVE - 1)) == 0) P.part[2 * (tid / WAVE) + slot] = a;
-}
-
 // ---- phase 4: recon, the residual, its square into the wave's partial, the recon part of G
 __device__ __forceinline__ void ph_resid(const Params& P, int tid, const Step& st) {
   const int n = P.n, K1 = P.K + 1, items = st.cnt * n;
@@ -217,7 +194,7 @@ __device__ __forceinline__ void ph_resid(const Params& P, int tid, const Step& s
     }
     a1 += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
   }
-  wave_partial(P, tid, a1, 0);
+  wave_partial(P.part, NW, tid, 0, a1);
 }
 
 // ---- phase 5: the hyperedges of every frame: loss partial and w
@@ -240,7 +217,7 @@ __device__ __forceinline__ void ph_edges(const Params& P, int tid, const Step& s
     a2 += diff * diff;
     if (!P.fwd_only) P.coef[(size_t)b * E + e] = dr > 0.0 ? s2 * diff / dr : 0.0;   // a coincident pair: 0, not NaN
   }
-  wave_partial(P, tid, a2, 1);
+  wave_partial(P.part, NW, tid, 1, a2);
 }
 
 // ---- phase 6: G += the hyperedge part, gathered over the atom's incidence row in edge order
@@ -262,30 +239,10 @@ __device__ __forceinline__ void ph_gather(const Params& P, int tid, const Step& 
   }
 }
 
-// torch.optim.Adam, single-tensor form: the scalars in double as the host computes them, the element in fp32 (the
-// gradient arrives rounded to fp32, as torch's does)
-struct Adam {
-  float w1, b2, w2, neg_step, bc2_sqrt, eps;
-};
-__device__ __forceinline__ Adam adam_of(const Params& P, long long step) {
-  const double t = (double)(step + 1);
-  const double bc1 = 1.0 - pow(P.beta1, t), bc2 = 1.0 - pow(P.beta2, t);
-  Adam a;
-  a.w1 = (float)(1.0 - P.beta1); a.b2 = (float)P.beta2; a.w2 = (float)(1.0 - P.beta2);
-  a.neg_step = (float)(-(P.lr / bc1)); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)P.eps;
-  return a;
-}
-__device__ __forceinline__ void adam_elem(const Adam& a, float& p, float g, float& m, float& v) {
-  m = m + a.w1 * (g - m);                                          // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * a.b2 + a.w2 * g * g;                                     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p = p + a.neg_step * (m / denom);                                // param.addcdiv_(exp_avg, denom, value = -step_size)
-}
-
-// ---- phase 8: dP(a,c) and Adam, one element per item
+// ---- phase 8: dP(a,c) and Adam, one element per item (the gradient arrives rounded to fp32, as torch's does)
 __device__ __forceinline__ void ph_update(const Params& P, int tid, const Step& st) {
   const int n = P.n, C = P.C, K = P.K, items = n * C;
-  const Adam ad = adam_of(P, st.step);
+  const Adam ad = adam_of(P.lr, P.beta1, P.beta2, P.eps, st.step);
   const bool probe = P.probe && st.last;
   const bool equi = P.kind != CGV_BASELINE_LINEAR;
   for (int it = tid; it < items; it += NT) {
@@ -310,8 +267,8 @@ __device__ __forceinline__ void ph_update(const Params& P, int tid, const Step& 
 
 __device__ __forceinline__ void ph_losses(const Params& P, int tid, const Step& st) {
   if (tid == 0) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int w = 0; w < NW; ++w) { s1 += P.part[2 * w]; s2 += P.part[2 * w + 1]; }     // wave order
+    double s1, s2;
+    partial_sums(P.part, NW, s1, s2);
     const double e = (double)st.cnt * (double)P.E;
     P.loss_log[2 * (size_t)st.local] = (float)(s1 / ((double)st.cnt * P.n * 3.0));
     P.loss_log[2 * (size_t)st.local + 1] = P.E > 0 ? (float)(s2 / e) : 0.f;          // no hyperedges: 0, not NaN
@@ -437,8 +394,6 @@ __global__ __launch_bounds__(LOSS_NT) void baseline_loss_k(const float* __restri
   losses[1] = E > 0 ? (float)(t2 / ((double)B * (double)E)) : 0.f;
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 inline int feature_count(int kind, int K, int knn) { return kind == CGV_BASELINE_LINEAR ? K : K * knn; }
 
 inline bool sizes_ok(int kind, int n, int K, int knn, int batch, int E) {
@@ -448,6 +403,27 @@ inline bool sizes_ok(int kind, int n, int K, int knn, int batch, int E) {
   const long long C = (long long)K * (kind == CGV_BASELINE_LINEAR ? 1 : knn);
   return C < CAP && (long long)n * C < CAP && (long long)batch * n < CAP && (long long)batch * C < CAP &&
          (long long)batch * E < CAP && 2ll * E < CAP;
+}
+
+struct Workspace {                       // byte offsets into the caller's workspace; the global form's arrays follow eid
+  size_t R, G, coef, rowptr, cursor, nbr, eid, cg, U, off, part, bytes;
+};
+inline Workspace baseline_workspace(int n, int K, int C, int batch, int E, int form) {
+  const size_t r = (size_t)batch * n * 3 * sizeof(double), e = (size_t)2 * std::max(E, 1) * sizeof(int);
+  Workspace L{};
+  Carve w;
+  L.R = w.take(r); L.G = w.take(r);
+  L.coef = w.take((size_t)batch * std::max(E, 1) * sizeof(double));
+  L.rowptr = w.take((size_t)(n + 1) * sizeof(int)); L.cursor = w.take((size_t)n * sizeof(int));
+  L.nbr = w.take(e); L.eid = w.take(e);
+  if (form != CGV_BASELINE_RESIDENT) {
+    L.cg = w.take((size_t)batch * (K + 1) * 3 * sizeof(double));
+    L.U = w.take((size_t)batch * C * 3 * sizeof(double));
+    L.off = w.take((size_t)batch * K * 3 * sizeof(double));
+    L.part = w.take((size_t)2 * NW * sizeof(double));
+  }
+  L.bytes = w.at;
+  return L;
 }
 
 }  // namespace baseline
@@ -465,14 +441,7 @@ int cgv_baseline_resident_fits(int kind, int n_atoms, int C, int batch) {
 
 size_t cgv_baseline_workspace_bytes(int kind, int n, int K, int knn, int batch, int E, int form) {
   if (!sizes_ok(kind, n, K, knn, batch, E)) return 0;
-  const size_t C = (size_t)feature_count(kind, K, knn);
-  size_t b = 2 * align256((size_t)batch * n * 3 * sizeof(double)) + align256((size_t)batch * std::max(E, 1) * sizeof(double)) +
-             align256((size_t)(n + 1) * sizeof(int)) + align256((size_t)n * sizeof(int)) +
-             2 * align256((size_t)2 * std::max(E, 1) * sizeof(int));
-  if (form != CGV_BASELINE_RESIDENT)
-    b += align256((size_t)batch * (K + 1) * 3 * sizeof(double)) + align256((size_t)batch * C * 3 * sizeof(double)) +
-         align256((size_t)batch * K * 3 * sizeof(double)) + align256((size_t)2 * NW * sizeof(double));
-  return b;
+  return baseline_workspace(n, K, feature_count(kind, K, knn), batch, E, form).bytes;
 }
 
 int cgv_baseline_steps(int kind, int form, int mode, float* B, float* mB, float* vB, const float* frames, int n_frames,
@@ -487,15 +456,10 @@ int cgv_baseline_steps(int kind, int form, int mode, float* B, float* mB, float*
   if (steps == 0) return 0;
   CGV_REQUIRE(B && frames && order && mapping && bead_sizes && loss_log && workspace && (E == 0 || edges), "null pointer");
   CGV_REQUIRE(mode == CGV_BASELINE_FORWARD || (mB && vB), "training needs both Adam moment arrays");
-  CGV_REQUIRE(order_len > 0 && order_len < (1ll << 31) && order_len % n_train == 0, "order table must hold whole epochs of n_train entries");
-  const int64_t spe = (n_train + batch - 1) / batch;
-  CGV_REQUIRE(step0 + steps <= (order_len / n_train) * spe, "steps run past the end of the order table");
-  const size_t need = cgv_baseline_workspace_bytes(kind, n, K, knn, batch, E, form);
-  if (workspace_bytes < need) {
-    cgv::set_error("cgv_baseline_steps: workspace of %zu bytes, need %zu", workspace_bytes, need);
-    return CGV_E_WORKSPACE;
-  }
+  if (int rc = schedule_check(__func__, order_len, n_train, batch, step0, steps)) return rc;
   const int C = feature_count(kind, K, knn);
+  const Workspace L = baseline_workspace(n, K, C, batch, E, form);
+  if (int rc = workspace_check(__func__, workspace_bytes, L.bytes)) return rc;
   Params P{};
   P.P = B; P.mP = mB; P.vP = vB;
   P.frames = frames; P.order = order; P.map = mapping; P.bsize = bead_sizes; P.edges = edges;
@@ -506,40 +470,24 @@ int cgv_baseline_steps(int kind, int form, int mode, float* B, float* mB, float*
   P.fwd_only = mode == CGV_BASELINE_FORWARD;
   P.gamma = gamma; P.lr = lr; P.beta1 = beta1; P.beta2 = beta2; P.eps = eps;
   char* ws = (char*)workspace;
-  const size_t rb = align256((size_t)batch * n * 3 * sizeof(double)), eb = align256((size_t)2 * std::max(E, 1) * sizeof(int));
-  P.R = (double*)ws; ws += rb; P.G = (double*)ws; ws += rb;
-  P.coef = (double*)ws; ws += align256((size_t)batch * std::max(E, 1) * sizeof(double));
-  P.rowptr = (int*)ws; ws += align256((size_t)(n + 1) * sizeof(int));
-  P.cursor = (int*)ws; ws += align256((size_t)n * sizeof(int));
-  P.nbr = (int*)ws; ws += eb; P.eid = (int*)ws; ws += eb;
+  P.R = (double*)(ws + L.R); P.G = (double*)(ws + L.G); P.coef = (double*)(ws + L.coef);
+  P.rowptr = (int*)(ws + L.rowptr); P.cursor = (int*)(ws + L.cursor); P.nbr = (int*)(ws + L.nbr); P.eid = (int*)(ws + L.eid);
   hipStream_t s = (hipStream_t)stream;
   if (form == CGV_BASELINE_RESIDENT) {
-    if (!cgv_baseline_resident_fits(kind, n, C, batch)) {
-      cgv::set_error("cgv_baseline_steps: %d x %d with batches of %d does not fit the resident form", n, C, batch);
-      return CGV_E_UNSUPPORTED;
-    }
+    if (!cgv_baseline_resident_fits(kind, n, C, batch)) return resident_refusal(__func__, n, C, batch);
     const size_t lds = resident_lds_floats(n, C, batch) * sizeof(float);
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)baseline_steps_k<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        cgv::set_error("cgv_baseline_steps: %zu bytes of LDS refused: %s", lds, hipGetErrorString(e));
-        return (int)e;
-      }
-    }
+    if (int rc = allow_lds(baseline_steps_k<true>, lds, __func__)) return rc;
     hipLaunchKernelGGL(baseline_steps_k<true>, dim3(1), dim3(NT), lds, s, P, (long long)step0, steps);
     return cgv::check_launch("cgv_baseline_steps");
   }
-  P.cg = (double*)ws; ws += align256((size_t)batch * (K + 1) * 3 * sizeof(double));
-  P.U = (double*)ws; ws += align256((size_t)batch * C * 3 * sizeof(double));
-  P.off = (double*)ws; ws += align256((size_t)batch * K * 3 * sizeof(double));
-  P.part = (double*)ws;
+  P.cg = (double*)(ws + L.cg); P.U = (double*)(ws + L.U); P.off = (double*)(ws + L.off); P.part = (double*)(ws + L.part);
   hipLaunchKernelGGL(baseline_steps_k<false>, dim3(1), dim3(NT), 0, s, P, (long long)step0, steps);
   return cgv::check_launch("cgv_baseline_steps (global)");
 }
 
 size_t cgv_baseline_loss_workspace_bytes(int b, int n, int E) {
   if (b <= 0 || n <= 0 || E < 0) return 0;
-  return 256 + align256((size_t)2 * b * sizeof(double)) + align256((size_t)b * std::max(E, 1) * sizeof(float));
+  return 256 + cgv::align256((size_t)2 * b * sizeof(double)) + cgv::align256((size_t)b * std::max(E, 1) * sizeof(float));
 }
 
 int cgv_baseline_loss(const float* xyz_recon, const float* xyz, const int32_t* edges, int b, int n, int E, float gamma,
@@ -547,13 +495,10 @@ int cgv_baseline_loss(const float* xyz_recon, const float* xyz, const int32_t* e
   CGV_REQUIRE(b > 0 && b <= 65535 && n > 0 && E >= 0, "bad size");
   CGV_REQUIRE((long long)b * n < CAP && (long long)b * E < CAP && (long long)n * E < (1ll << 28), "problem beyond the cap (b n, b E < 2^24; n E < 2^28)");
   CGV_REQUIRE(xyz_recon && xyz && losses && grad && workspace && (E == 0 || edges), "null pointer");
-  if (workspace_bytes < cgv_baseline_loss_workspace_bytes(b, n, E)) {
-    cgv::set_error("cgv_baseline_loss: workspace of %zu bytes, need %zu", workspace_bytes, cgv_baseline_loss_workspace_bytes(b, n, E));
-    return CGV_E_WORKSPACE;
-  }
+  if (int rc = workspace_check(__func__, workspace_bytes, cgv_baseline_loss_workspace_bytes(b, n, E))) return rc;
   char* ws = (char*)workspace;
   unsigned* ticket = (unsigned*)ws; ws += 256;
-  double* partial = (double*)ws; ws += align256((size_t)2 * b * sizeof(double));
+  double* partial = (double*)ws; ws += cgv::align256((size_t)2 * b * sizeof(double));
   hipLaunchKernelGGL(baseline_loss_k, dim3(b), dim3(LOSS_NT), 0, (hipStream_t)stream, xyz_recon, xyz, edges, n, E, gamma, losses,
                      grad, ticket, partial, (float*)ws);
   return cgv::check_launch("cgv_baseline_loss");

@@ -35,17 +35,17 @@
 // launch of 10 steps and ten launches of one draw the same numbers and no noise tensor exists.  A word's top 23 bits b
 // give u = (b + 0.5) / 2^23, exact in fp32 and inside the OPEN interval; g = -log(-log(u)) is evaluated in fp64 and rounded
 // once, so that a host restatement in fp64 reproduces the bits (tests/cgae_restatement.py).
+// The schedule rule, Adam, the loss partials and the host checks are steploop_dev.h's, shared with K19.
 #include <algorithm>
 
-#include "cgv_common.h"
+#include "steploop_dev.h"
 
 namespace cgv {
 namespace cgae {
 
-constexpr int NT = 512;                  // threads of the resident workgroup and of every streamed block
-constexpr int NW = NT / WAVE;
+using namespace steploop;                // NT, NW, LDS_LIMIT, Step, step_of, Adam, wave_partial, the host checks
+
 constexpr int MAX_BLOCKS = 1024;         // streamed form: cap of a phase's grid (items are strided over it)
-constexpr size_t LDS_LIMIT = 160 * 1024; // one workgroup may hold all of a CU's LDS
 
 struct Params {
   float *W, *D, *mW, *vW, *mD, *vD;      // [n,K] [K,n] and the moments of each
@@ -68,24 +68,6 @@ struct Params {
 struct Ctx {
   int tid, nthreads;
 };
-
-struct Step {
-  long long step;                        // index in the whole schedule (Adam's step count is step + 1)
-  int local;                             // index within this call
-  int off, cnt;                          // the batch: order[off .. off + cnt)
-  int last;                              // last step of this call (the probe is written then)
-};
-
-__host__ __device__ inline Step step_of(int n_train, int batch, long long step, int local, int last) {
-  const int spe = (n_train + batch - 1) / batch;
-  const long long epoch = step / spe;
-  const int si = (int)(step % spe);
-  Step st;
-  st.step = step; st.local = local; st.last = last;
-  st.off = (int)(epoch * n_train) + si * batch;                    // the host checked that the table fits an int
-  st.cnt = min(batch, n_train - si * batch);                       // the last, partial batch of an epoch is kept
-  return st;
-}
 
 __device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
   const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0], p1 = (unsigned long long)0xCD9E8D57u * c[2];
@@ -110,8 +92,7 @@ __device__ __forceinline__ void gumbel_quad(unsigned seed_lo, unsigned seed_hi, 
 }
 
 __device__ __forceinline__ const float* frame_of(const Params& P, const Step& st, int b) {
-  const int f = min(max(P.order[st.off + b], 0), P.n_frames - 1);   // a bad table entry must not become a wild read
-  return P.frames + (size_t)f * P.n * 3;
+  return steploop::frame_of(P.frames, P.order, P.n_frames, P.n, st, b);
 }
 
 // ---- phase 1: M = softmax(W + g), one row per item
@@ -180,13 +161,13 @@ __device__ __forceinline__ void ph_resid(const Params& P, const Ctx& c, const St
     st3(P.e2 + (size_t)it * 3, s2 * l0, s2 * l1, s2 * l2);
   }
 #pragma unroll
-  for (int o = WAVE / 2; o > 0; o >>= 1) {                          // fixed tree inside the wave
+  for (int o = WAVE / 2; o > 0; o >>= 1) {                          // steploop's wave_partial, both sums side by side
     a1 += __shfl_xor(a1, o, WAVE);
     a2 += __shfl_xor(a2, o, WAVE);
   }
   if ((c.tid & (WAVE - 1)) == 0) {
     const int w = c.tid / WAVE;
-    if (w < P.nparts) { P.part[2 * w] = a1; P.part[2 * w + 1] = a2; }
+    if (w < P.nparts) { P.part[2 * w] = a1; P.part[2 * w + 1] = a2; }   // streamed: blocks x NW slots
   }
 }
 
@@ -240,29 +221,10 @@ __device__ __forceinline__ void ph_dm(const Params& P, const Ctx& c, const Step&
   }
 }
 
-// torch.optim.Adam, single-tensor form: the scalars in double as the host computes them, the element in fp32
-struct Adam {
-  float w1, b2, w2, neg_step, bc2_sqrt, eps;
-};
-__device__ __forceinline__ Adam adam_of(const Params& P, long long step) {
-  const double t = (double)(step + 1);
-  const double bc1 = 1.0 - pow(P.beta1, t), bc2 = 1.0 - pow(P.beta2, t);
-  Adam a;
-  a.w1 = (float)(1.0 - P.beta1); a.b2 = (float)P.beta2; a.w2 = (float)(1.0 - P.beta2);
-  a.neg_step = (float)(-(P.lr / bc1)); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)P.eps;
-  return a;
-}
-__device__ __forceinline__ void adam_elem(const Adam& a, float& p, float g, float& m, float& v) {
-  m = m + a.w1 * (g - m);                                          // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * a.b2 + a.w2 * g * g;                                     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p = p + a.neg_step * (m / denom);                                // param.addcdiv_(exp_avg, denom, value = -step_size)
-}
-
 // ---- phase 6: softmax backward + Adam on W (a row per item), Adam on D (an element per item), the step's losses
 __device__ __forceinline__ void ph_update(const Params& P, const Ctx& c, const Step& st) {
   const int K = P.K, n = P.n;
-  const Adam a = adam_of(P, st.step);
+  const Adam a = adam_of(P.lr, P.beta1, P.beta2, P.eps, st.step);
   const bool probe = P.probe && st.last;
   for (int i = c.tid; i < n; i += c.nthreads) {
     const float* m = P.M + (size_t)i * K;
@@ -284,8 +246,8 @@ __device__ __forceinline__ void ph_update(const Params& P, const Ctx& c, const S
   if (probe)
     for (int e = c.tid; e < st.cnt * K * 3; e += c.nthreads) P.probe[(size_t)3 * n * K + e] = P.cg[e];
   if (c.tid == 0) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int w = 0; w < P.nparts; ++w) { s1 += P.part[2 * w]; s2 += P.part[2 * w + 1]; }   // wave order
+    double s1, s2;
+    partial_sums(P.part, P.nparts, s1, s2);
     const float2 out = make_float2((float)(s1 / ((double)st.cnt * n * 3.0)), (float)(s2 / ((double)st.cnt * n)));
     *reinterpret_cast<float2*>(P.loss_log + 2 * (size_t)st.local) = out;
   }
@@ -357,7 +319,21 @@ __global__ __launch_bounds__(256) void cgae_noise_k(unsigned seed_lo, unsigned s
 
 inline int blocks_for(long long items) { return (int)std::min<long long>(MAX_BLOCKS, std::max<long long>(1, (items + NT - 1) / NT)); }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Workspace {                       // byte offsets into the caller's workspace; the streamed form's arrays follow e1 / e2
+  size_t e1, e2, M, dD, dM, cg, dcg, csum, part, bytes;
+};
+inline Workspace cgae_workspace(int n, int K, int batch, int form) {
+  const size_t e = (size_t)batch * n * 3 * sizeof(float), nk = (size_t)n * K * sizeof(float), c = (size_t)batch * K * 3 * sizeof(float);
+  Workspace L{};
+  Carve w;
+  L.e1 = w.take(e); L.e2 = w.take(e);
+  if (form != CGV_CGAE_RESIDENT) {
+    L.M = w.take(nk); L.dD = w.take(nk); L.dM = w.take(nk); L.cg = w.take(c); L.dcg = w.take(c);
+    L.csum = w.take((size_t)K * sizeof(float)); L.part = w.take((size_t)2 * MAX_BLOCKS * NW * sizeof(double));
+  }
+  L.bytes = w.at;
+  return L;
+}
 
 }  // namespace cgae
 }  // namespace cgv
@@ -374,11 +350,7 @@ int cgv_cgae_resident_fits(int n, int K, int batch) {
 
 size_t cgv_cgae_workspace_bytes(int n, int K, int batch, int form) {
   if (n <= 0 || K <= 0 || batch <= 0) return 0;
-  size_t b = 2 * align256((size_t)batch * n * 3 * sizeof(float));                       // e1, e2
-  if (form != CGV_CGAE_RESIDENT)
-    b += 3 * align256((size_t)n * K * sizeof(float)) + 2 * align256((size_t)batch * K * 3 * sizeof(float)) +
-         align256((size_t)K * sizeof(float)) + align256((size_t)2 * MAX_BLOCKS * NW * sizeof(double));
-  return b;
+  return cgae_workspace(n, K, batch, form).bytes;
 }
 
 int cgv_cgae_steps(int form, float* W, float* D, float* mW, float* vW, float* mD, float* vD, const float* frames,
@@ -391,13 +363,9 @@ int cgv_cgae_steps(int form, float* W, float* D, float* mW, float* vW, float* mD
   CGV_REQUIRE((int64_t)n * K < (1ll << 24) && (int64_t)batch * n < (1ll << 24) && (int64_t)batch * K < (1ll << 24), "problem too large");
   if (steps == 0) return 0;
   CGV_REQUIRE(W && D && mW && vW && mD && vD && frames && order && loss_log && workspace, "null pointer");
-  CGV_REQUIRE(order_len > 0 && order_len < (1ll << 31) && order_len % n_train == 0, "order table must hold whole epochs of n_train entries");
-  const int64_t spe = (n_train + batch - 1) / batch;
-  CGV_REQUIRE(step0 + steps <= (order_len / n_train) * spe, "steps run past the end of the order table");
-  if (workspace_bytes < cgv_cgae_workspace_bytes(n, K, batch, form)) {
-    cgv::set_error("cgv_cgae_steps: workspace of %zu bytes, need %zu", workspace_bytes, cgv_cgae_workspace_bytes(n, K, batch, form));
-    return CGV_E_WORKSPACE;
-  }
+  if (int rc = schedule_check(__func__, order_len, n_train, batch, step0, steps)) return rc;
+  const Workspace L = cgae_workspace(n, K, batch, form);
+  if (int rc = workspace_check(__func__, workspace_bytes, L.bytes)) return rc;
   hipStream_t s = (hipStream_t)stream;
   Params P{};
   P.W = W; P.D = D; P.mW = mW; P.vW = vW; P.mD = mD; P.vD = vD;
@@ -406,29 +374,16 @@ int cgv_cgae_steps(int form, float* W, float* D, float* mW, float* vW, float* mD
   P.reg_weight = reg_weight; P.lr = lr; P.beta1 = beta1; P.beta2 = beta2; P.eps = eps;
   P.seed_lo = (unsigned)seed; P.seed_hi = (unsigned)(seed >> 32);
   char* ws = (char*)workspace;
-  const size_t eb = align256((size_t)batch * n * 3 * sizeof(float));
-  P.e1 = (float*)ws; ws += eb; P.e2 = (float*)ws; ws += eb;
+  P.e1 = (float*)(ws + L.e1); P.e2 = (float*)(ws + L.e2);
   if (form == CGV_CGAE_RESIDENT) {
-    if (!cgv_cgae_resident_fits(n, K, batch)) {
-      cgv::set_error("cgv_cgae_steps: %d x %d with batches of %d does not fit the resident form", n, K, batch);
-      return CGV_E_UNSUPPORTED;
-    }
+    if (!cgv_cgae_resident_fits(n, K, batch)) return resident_refusal(__func__, n, K, batch);
     const size_t lds = resident_lds_floats(n, K, batch) * sizeof(float);
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)cgae_resident_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        cgv::set_error("cgv_cgae_steps: %zu bytes of LDS refused: %s", lds, hipGetErrorString(e));
-        return (int)e;
-      }
-    }
+    if (int rc = allow_lds(cgae_resident_k, lds, __func__)) return rc;
     hipLaunchKernelGGL(cgae_resident_k, dim3(1), dim3(NT), lds, s, P, (long long)step0, steps);
     return cgv::check_launch("cgv_cgae_steps");
   }
-  const size_t nkb = align256((size_t)n * K * sizeof(float)), cb = align256((size_t)batch * K * 3 * sizeof(float));
-  P.M = (float*)ws; ws += nkb; P.dD = (float*)ws; ws += nkb; P.dM = (float*)ws; ws += nkb;
-  P.cg = (float*)ws; ws += cb; P.dcg = (float*)ws; ws += cb;
-  P.csum = (float*)ws; ws += align256((size_t)K * sizeof(float));
-  P.part = (double*)ws;
+  P.M = (float*)(ws + L.M); P.dD = (float*)(ws + L.dD); P.dM = (float*)(ws + L.dM);
+  P.cg = (float*)(ws + L.cg); P.dcg = (float*)(ws + L.dcg); P.csum = (float*)(ws + L.csum); P.part = (double*)(ws + L.part);
   const long long nk = (long long)n * K;
   for (int i = 0; i < steps; ++i) {
     const Step st = step_of(n_train, batch, step0 + i, i, i == steps - 1);

@@ -29,6 +29,8 @@ inline int check_launch(const char* what) {
 
 constexpr int WAVE = 64;
 
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }   // workspace arrays start on 256-byte boundaries
+
 // Edge-geometry record layout (floats):  [0,R) a_n ; [R] env ; pad to even ; [U,U+6) ux,uy,uz,ux,uy,uz
 // The unit vector is stored twice so that every adjacent pair (ux,uy) (uz,ux) (uy,uz) is an
 // aligned 64-bit scalar-register pair: the packed-fp32 kernels (v_pk_fma_f32, two channels per

@@ -48,7 +48,6 @@ __constant__ unsigned long long* g_k2e_clock = nullptr;
 
 typedef float q4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u4v __attribute__((__vector_size__(16)));
-static inline size_t bal_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr int SC1 = 16;                              // buffer cache policy: agent scope (sc1) -- past the XCD's own L2
 
 // A wave's partial sums of one group: [2 RB][64 lanes][4 floats] = RB x 2 KB; slot s of wave w at (w * 2 + s) * RB * 2 KB
@@ -358,7 +357,7 @@ int cgv_equi_msg_balanced_supported(int n_feat, int n_rbf, int rb) { return cgv_
 size_t cgv_equi_msg_balanced_workspace_bytes(int n_dst, int n_feat, int rb) {
   if (n_dst <= 0 || n_feat <= 0 || rb <= 0) return 0;
   const size_t tiles = ((size_t)n_feat + 127) / 128, groups = ((size_t)n_dst + rb - 1) / rb;
-  const size_t tickets = cgv::bal_align256(tiles * groups * sizeof(unsigned));
+  const size_t tickets = cgv::align256(tiles * groups * sizeof(unsigned));
   const size_t waves = (size_t)(cgv::cu_count() & ~7) * cgv::BAL_BPC_MAX * cgv::BAL_WPB;
   return tickets + waves * 2 * (size_t)rb * 2048;
 }
@@ -387,7 +386,7 @@ int cgv_equi_msg_fwd_balanced(const float* phi, const float* v, const float* geo
   CGV_REQUIRE(tiles <= blocks, "more channel tiles than blocks");
   const int bpt = blocks / tiles;
   unsigned* ticket = reinterpret_cast<unsigned*>(workspace);
-  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + cgv::bal_align256((size_t)tiles * groups * sizeof(unsigned)));
+  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + cgv::align256((size_t)tiles * groups * sizeof(unsigned)));
   CGV_DISPATCH_RBF(n_rbf, {
     hipLaunchKernelGGL((cgv::equi_msg_fwd_bal_k<RBF, 2, cgv::BAL_WPB>), dim3(blocks), dim3(64 * cgv::BAL_WPB), 0, st, phi, v, geom_g,
                        rowptr_d, src_g, dst_g, Wd, bd, ds, dv, n_feat, n_dst, tiles, bpt, s_res, v_res, part, ticket);

@@ -115,8 +115,6 @@ __global__ void csr_rowptr(const int* __restrict__ sorted_keys, int n, int n_row
   rowptr[i] = lo;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static hipError_t sort_temp_bytes(int n, size_t* bytes) {
   int* k = nullptr;
   *bytes = 0;

@@ -18,7 +18,7 @@
 //                          the component has split: both parts are relabelled with their lowest atom index and the
 //                          component counter goes up.  Mode 0 labels the whole graph (one BFS per component).
 // All three return at once when the counter has reached n_cgs, so a batch of removals may be enqueued blind.
-#include "cgv_common.h"
+#include "steploop_dev.h"
 
 namespace cgv {
 
@@ -303,17 +303,6 @@ newman_components_k(const int32_t* __restrict__ rowptr, const int32_t* __restric
 
 static int nm_resident_fits(int n, int m) { return nm_layout(n, m).bytes <= NM_LDS_LIMIT; }
 
-template <typename K>
-static int nm_allow_lds(K kernel, size_t lds, const char* what) {
-  if (lds <= 64 * 1024) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    set_error("%s: %zu bytes of LDS refused: %s", what, lds, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
 static int nm_check(int n, int m, int form, const void* workspace, size_t workspace_bytes, int groups, const char* who) {
   if (n < 1 || n > NM_MAX_ATOMS || m < 0 || m > NM_MAX_EDGES) {
     set_error("%s: 1 <= n <= %d atoms and 0 <= m <= %d edges", who, NM_MAX_ATOMS, NM_MAX_EDGES);
@@ -345,8 +334,7 @@ static int nm_launch_betweenness(const int32_t* rowptr, const int32_t* col, cons
   double* partial = (double*)(ws + W.partial);
   if (form == CGV_NEWMAN_RESIDENT) {
     const size_t lds = nm_layout(n, m).bytes;
-    int rc = nm_allow_lds(newman_betweenness_k<true>, lds, "cgv_newman_betweenness");
-    if (rc) return rc;
+    if (int rc = steploop::allow_lds(newman_betweenness_k<true>, lds, "cgv_newman_betweenness")) return rc;
     hipLaunchKernelGGL(newman_betweenness_k<true>, dim3((unsigned)g), dim3(threads), lds, st, rowptr, col, edge_id, alive, n, m,
                        chunk, state, n_cgs, partial, (char*)nullptr);
   } else {
@@ -363,8 +351,7 @@ static int nm_launch_components(const int32_t* rowptr, const int32_t* col, const
   int *mark = (int*)(ws + W.mark), *queue = (int*)(ws + W.queue);
   const size_t lds = (size_t)n * 8;
   if (form == CGV_NEWMAN_RESIDENT && lds <= NM_LDS_LIMIT - 8 * 1024) {      // mark + queue beside 4 KB of statics
-    int rc = nm_allow_lds(newman_components_k<true>, lds, "cgv_newman_components");
-    if (rc) return rc;
+    if (int rc = steploop::allow_lds(newman_components_k<true>, lds, "cgv_newman_components")) return rc;
     hipLaunchKernelGGL(newman_components_k<true>, dim3(1), dim3(NM_WIDE), lds, st, rowptr, col, edge_id, edges, alive, n, labels,
                        state, n_cgs, mode, log, mark, queue);
   } else {

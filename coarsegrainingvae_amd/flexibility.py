@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, ensemble, options
+from .steploop import forced_form
 from .coverage import rmsd_matrix
 from .ensemble import check_sets, device_of, groups_of, read_back, scalar_block, select_atoms, structures
 
@@ -41,7 +42,7 @@ def limits() -> Dict[str, int]:
 def _form(n_atoms: int) -> int:
     """The form ``cgv_align_accumulate`` is asked for: option ``align_form`` (0 the library's rule, 1 a wave per
     structure, 2 a block per structure); forcing the wave form on a structure it does not hold is an error."""
-    form = int(options.get("align_form"))
+    form = forced_form("align_form", lambda: int(options.get("align_form")))     # 0: the library applies its own rule
     if form not in (0, 1, 2):
         raise ValueError("option align_form must be 0 (rule), 1 (wave) or 2 (block)")
     if form == 1 and not _lib.load().cgv_align_wave_fits(int(n_atoms)):

@@ -125,6 +125,53 @@ def test_determinism_and_agreement_of_the_forms(golden):
                 assert torch.equal(a, b)
 
 
+def _schedule_case(kind):
+    """The shared schedule rule on the smallest table that reaches it: 5 atoms in beads [0,0,1,1,1], 3 hyperedges, 8 frames,
+    two epochs of n_train = 7 in batches of 3 (3 steps per epoch, the last batch of an epoch holds 1 frame), 6 steps.
+    Returns the inputs and the fp64 restatement walking the same table: B after the 6 steps and the [6, 2] loss log."""
+    n, K, knn, batch, gamma, lr = 5, 2, 1, 3, 0.5, 1e-3
+    gen = torch.Generator().manual_seed(17)
+    xyz = (torch.cumsum(torch.randn(8, n, 3, generator=gen) * 1.5, dim=1) + 3.0).numpy()     # coordinates of a few Angstrom
+    mapping, edges = np.array([0, 0, 1, 1, 1]), np.array([[0, 1], [1, 2], [2, 4]])
+    order = np.array([[3, 0, 7, 5, 1, 6, 2], [4, 2, 0, 6, 7, 1, 3]], dtype=np.int32)
+    B0 = (0.01 * torch.randn(*((K, n) if kind == "linear" else (n, K * knn)), generator=gen)).numpy()
+    batches = [xyz[row[s:s + batch]] for row in order for s in range(0, order.shape[1], batch)]
+    (want_B,), want_log = R.adam_steps(kind, [B0], batches, mapping, edges, gamma, K, knn, lr=lr)
+    return dict(xyz=xyz, mapping=mapping, edges=edges, order=order, B=B0, K=K, knn=knn, batch=batch, gamma=gamma, lr=lr), want_B, want_log
+
+
+@pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
+@pytest.mark.parametrize("kind", R.LINEAR_KINDS)
+def test_schedule_partial_batches_and_epoch_boundary(golden, kind, form):
+    """(a) one call of 6 steps = calls of 1, 2 and 3 steps, bit for bit, in B, both Adam moments and the loss log; (b) B and
+    every row of the loss log against the fp64 restatement walking the same table, under the bound of
+    test_step_parity_with_the_reference: four times the reference's own deviation as stored in a fixture (_allowed).  No
+    fixture holds this schedule; the bounds are those of the kind's knn = 1, gamma = 0.5 step fixture, the 6-step B under its
+    B_after10 entry (the loosest of that horizon) and the loss rows under loss_recon / loss_dist."""
+    case, want_B, want_log = _schedule_case(kind)
+    f = golden(f"g19_baseline_step_{kind}_n22_k3_knn1_g05")
+    runs = []
+    for split in ((6,), (1, 2, 3)):
+        pool = B.FixedPool(case["mapping"], case["K"])
+        m = B.Baseline(pool, case["K"], 5) if kind == "linear" else B.EquiLinear(pool, case["K"], 5, False, case["knn"])
+        m.load_reference_state({"B": torch.from_numpy(case["B"]).clone()})
+        m, logs, done = m.cuda(), [], 0
+        for cnt in split:
+            logs.append(m.run_steps(case["xyz"], case["order"], case["batch"], done, cnt, mode=B.TRAIN, lr=case["lr"],
+                                    gamma=case["gamma"], edges=case["edges"], form=form)[0])
+            done += cnt
+        runs.append((m.B.detach().cpu(), m.moments[0].cpu(), m.moments[1].cpu(), torch.cat(logs).cpu()))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+    got_B, got_log = runs[0][0].numpy(), runs[0][3].numpy()
+    assert got_log.shape == (6, 2) and not np.array_equal(got_B, case["B"])
+    devs = {"B_after10": R.rel_dev(got_B, want_B), "loss_recon": max(R.rel_dev(got_log[s, 0], want_log[s, 0]) for s in range(6)),
+            "loss_dist": max(R.rel_dev(got_log[s, 1], want_log[s, 1]) for s in range(6))}
+    print(f"SCHEDULE {kind} {B.FORM_NAMES[form]} " + " ".join(f"{q}={d:.2e}/{_allowed(f, q):.2e}" for q, d in devs.items()))
+    for q, d in devs.items():
+        assert d <= _allowed(f, q), (q, d, _allowed(f, q))
+
+
 @pytest.mark.parametrize("form", FORMS, ids=FORM_IDS)
 def test_forward_mode(golden, form):
     f = golden("g19_baseline_step_equilinear_n22_k3_knn2_g05")

@@ -82,6 +82,60 @@ def test_one_launch_of_ten_steps_equals_ten_launches(golden, form):
     assert not torch.equal(ln.W.cpu(), runs[0][0])                  # another seed, other noise
 
 
+def _schedule_case():
+    """The shared schedule rule on the smallest table that reaches it: 5 atoms, 2 beads, 8 frames, two epochs of n_train = 7
+    in batches of 3, so every epoch is 3 steps and its last batch holds 1 frame; 6 steps cross the epoch boundary.  Returns
+    the inputs and the fp64 restatement walking the same table: W, D after the 6 steps and the [6, 2] loss log."""
+    n, K, T, batch, reg, lr = 5, 2, 8, 3, 0.25, 4e-3
+    gen = torch.Generator().manual_seed(11)
+    W, D = torch.randn(n, K, generator=gen), torch.randn(K, n, generator=gen)
+    X = torch.cumsum(torch.randn(T, n, 3, generator=gen) * 1.5, dim=1) + 3.0          # coordinates of a few Angstrom
+    order = np.array([[3, 0, 7, 5, 1, 6, 2], [4, 2, 0, 6, 7, 1, 3]], dtype=np.int32)
+    noise = torch.from_numpy(np.stack([R.gumbel_noise(21, s, n, K) for s in range(6)]))
+    Xc = (X - X.mean(1, keepdim=True)).double()                                          # as Learner centres them, in fp32
+    W64, D64 = W.double().clone().requires_grad_(True), D.double().clone().requires_grad_(True)
+    opt, log, step = torch.optim.Adam([W64, D64], lr=lr), [], 0
+    for row in order:
+        for s in range(0, order.shape[1], batch):
+            opt.zero_grad()
+            out = R.forward(W64, D64, Xc[row[s:s + batch]], noise[step].double(), reg)
+            out["loss"].backward()
+            opt.step()
+            log.append((float(out["loss_recon"].detach()), float(out["loss_reg"].detach())))
+            step += 1
+    want = {"W": W64.detach().numpy(), "D": D64.detach().numpy(), "loss_log": np.array(log)}
+    return dict(W=W, D=D, X=X, order=order, batch=batch, reg=reg, lr=lr, noise=noise), want
+
+
+@pytest.mark.parametrize("form", FORMS, ids=["resident", "streamed"])
+def test_schedule_partial_batches_and_epoch_boundary(golden, form):
+    """(a) one call of 6 steps = calls of 1, 2 and 3 steps, bit for bit, in W, D and the loss log; (b) W, D and every row of
+    the loss log against the fp64 restatement walking the same table, under the allowance of
+    test_step_parity_with_the_reference (four times the reference's own fp32 deviation, from the fixtures).  The fixtures
+    hold parameters after 1 and 10 steps; the 6-step parameters go under the W_after10 / D_after10 entries, the loosest of
+    that horizon, and the loss rows under loss_recon / loss_reg."""
+    case, want = _schedule_case()
+    runs = []
+    for split in ((6,), (1, 2, 3)):
+        ln = cgmap.Learner(case["X"], case["W"], case["D"], case["order"], case["batch"], case["reg"], lr=case["lr"], seed=0, form=form)
+        assert ln.total_steps == 6
+        done = 0
+        for cnt in split:
+            ln.run(cnt, noise=case["noise"][done:done + cnt])
+            done += cnt
+        runs.append((ln.W.cpu(), ln.D.cpu(), ln.loss_log.cpu()))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+    allowed = _allowed(golden)
+    got_W, got_D, got_log = (t.numpy() for t in runs[0])
+    devs = {"W_after10": R.rel_dev(got_W, want["W"]), "D_after10": R.rel_dev(got_D, want["D"]),
+            "loss_recon": max(R.rel_dev(got_log[s, 0], want["loss_log"][s, 0]) for s in range(6)),
+            "loss_reg": max(R.rel_dev(got_log[s, 1], want["loss_log"][s, 1]) for s in range(6))}
+    print(f"SCHEDULE {cgmap.FORM_NAMES[form]} " + " ".join(f"{q}={d:.2e}/{allowed[q]:.2e}" for q, d in devs.items()))
+    for q, d in devs.items():
+        assert d <= allowed[q], (q, d, allowed[q])
+
+
 @pytest.mark.parametrize("seed,step,n,K", [(0, 0, 22, 3), (123, 43499, 166, 6), ((1 << 40) + 5, (1 << 33) + 1, 37, 9)])
 def test_kernel_noise_equals_the_restatement_bit_for_bit(seed, step, n, K):
     got = cgmap.kernel_noise(seed, step, 2, n, K).cpu().numpy()
