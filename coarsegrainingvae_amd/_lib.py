@@ -66,11 +66,6 @@ PROTOTYPES = {
     "cgv_equi_msg_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_int64, C.c_int64, _p, _p, _p]),
     "cgv_equi_msg_grouped_supported": (_i, [_i, _i, _i]),
     "cgv_equi_msg_fwd_grouped": (_i, [_p] * 9 + [_i, _i, _i, _i, C.c_int64, C.c_int64, _p, _p, _p]),
-    "cgv_equi_msg_grouped_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
-    "cgv_equi_msg_fwd_grouped_parts": (_i, [_p] * 9 + [_i, _i, _i, _i, C.c_int64, C.c_int64, _p, _p, _i, _p, C.c_size_t, _p]),
-    "cgv_equi_msg_balanced_supported": (_i, [_i, _i, _i]),
-    "cgv_equi_msg_balanced_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "cgv_equi_msg_fwd_balanced": (_i, [_p] * 10 + [_i, _i, _i, _i, C.c_int64, _p, _p, _p, C.c_size_t, _p]),
     "cgv_equi_msg_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
     "cgv_equi_msg_bwd": (_i, [_p] * 13 + [_i, _i, _i, C.c_int64, C.c_int64, _p, _sz, _p]),
     "cgv_pseudo_msg_fwd": (_i, [_p] * 14 + [_i, _i, _i, _i, _p]),
@@ -119,9 +114,6 @@ PROTOTYPES = {
     "cgv_prior_msg_bwd": (_i, [_p] * 8 + [_i, C.c_int64] + [_p] * 6 + [C.c_int64, _i, _i, _i, _i, _p]),
     "cgv_decoder_uv_fwd": (_i, [_p, _p, _p, _p, _i, _i, _p]),
     "cgv_decoder_gate_fwd": (_i, [_p] * 9 + [_i, _i, _p]),
-    "cgv_update_rows_fused_supported": (_i, [_i, _i]),
-    "cgv_update_uv_norm_fwd_fused": (_i, [_p] * 5 + [_i, _i, _p]),
-    "cgv_update_gate_fwd_fused": (_i, [_p] * 9 + [_i, _i, _p]),
     "cgv_decoder_gate_bwd": (_i, [_p, _p, _p, _p, _i, C.c_int64, _p, _p, _p, _p, _p, _p, C.c_int64, _i, _i, _p]),
     "cgv_decoder_dense_bwd": (_i, [_p, _i, C.c_int64, _p, _i, _p, _p, _p, C.c_int64, _i, _i, _i, _p]),
     "cgv_decoder_uv_bwd": (_i, [_p, _i, C.c_int64, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int64, _i, _i, _p]),
@@ -286,10 +278,10 @@ PROTOTYPES = {
 
 
 # include/cgvae_hip.h: CGV_OPT_* (A/B switches of the launchers; defaults in csrc/api.cpp)
-OPTIONS = {"msg_fwd_split": 0, "msg_bwd_split": 1, "msg_fwd_kernel": 2, "grp_waves": 3, "grp_records": 4, "csr_build": 5,
-           "pseudo_chunks": 6, "wgrad_tiling": 7, "tile_fwd_lds_min": 8, "bwd_input_waves": 9, "pseudo_fwd": 10, "decoder_fat": 11, "decoder_wlds": 12, "skinny_rows": 13,
-           "tile_fwd_bal": 14, "optim_one_launch": 15, "decoder_colsplit": 16, "decoder_nodesplit": 17,
-           "msg_fwd_balanced": 18, "bwd_input_split": 19, "msg_bwd_mfma": 20, "streamk": 21}
+OPTIONS = {"msg_fwd_split": 0, "msg_bwd_split": 1, "csr_build": 2, "pseudo_chunks": 3, "wgrad_tiling": 4, "tile_fwd_lds_min": 5,
+           "bwd_input_waves": 6, "pseudo_fwd": 7, "decoder_fat": 8, "decoder_wlds": 9, "skinny_rows": 10, "tile_fwd_bal": 11,
+           "optim_one_launch": 12, "decoder_colsplit": 13, "decoder_nodesplit": 14, "bwd_input_split": 15, "msg_bwd_mfma": 16,
+           "streamk": 17}
 
 
 def set_option(name: str, value: int) -> None:
@@ -329,7 +321,7 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        if lib.cgv_version() < 100:
+        if lib.cgv_version() < 101:                 # 101 renumbered the options: an older library would mis-set switches
             raise RuntimeError("libcgvae_hip.so is older than this package")
         _lib = lib
     return _lib

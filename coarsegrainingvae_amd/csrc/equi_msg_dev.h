@@ -136,7 +136,7 @@ __device__ __forceinline__ void stpair(float* base, const ChanPair& cp, f2 x) {
   else { base[cp.c] = x.x; if (cp.live1) base[cp.c1] = x.y; }
 }
 
-// ---- the shared-source walk's per-wave state and edge math (equi_msg_grp.hip, equi_msg_bal.hip)
+// ---- the shared-source walk's per-wave state and edge math (equi_msg_grp.hip)
 struct RowBuf { f2 p0, p1, p2, A, B, C; };
 struct Acc { f2 s, A, B, C; };
 

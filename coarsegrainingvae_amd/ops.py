@@ -54,46 +54,6 @@ def _grouped_forward_usable(plan, geom, F, tensors8, Wd) -> bool:
     return all(t is None or t.data_ptr() % 8 == 0 for t in tensors8)
 
 
-_BAL_WS = {}
-_GRP_WS = {}
-
-
-def grouped_parts(plan) -> int:
-    """Blocks per (group, channel tile) of the shared-source forward.  1: several blocks per group measured level with one
-    on every workload (chignolin 43.9 / 41.9 / 43.4 / 47.8 us for 1 / 2 / 3 / 4 parts, 2000 atoms 605 / 605 / 618 / 632,
-    dipeptide 22 / 29 / 36 / 47: profiles/r05_k2_parts_ab.txt) -- the launch is bound by packed-FMA issue at the clock the
-    chip sustains under it, not by how its blocks are cut; ``fwd_parts`` keeps the alternative for A/B runs."""
-    p = options.HOST["fwd_parts"]
-    return min(int(p), 4) if p >= 1 and plan.group_rb == 2 else 1
-
-
-def _grouped_workspace(device, n_dst, F, rb, parts):
-    """Tickets + partial-sum slots of cgv_equi_msg_fwd_grouped_parts: zeroed ONCE per (device, stream, shape); same rules
-    as ``_balanced_workspace`` below."""
-    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream), int(n_dst), int(F), int(rb), int(parts))
-    ws = _GRP_WS.get(key)
-    if ws is None:
-        ws = torch.zeros(int(_lib.load().cgv_equi_msg_grouped_workspace_bytes(int(n_dst), int(F), int(rb), int(parts))),
-                         dtype=torch.uint8, device=device)
-        if not torch.cuda.is_current_stream_capturing():
-            _GRP_WS[key] = ws
-    return ws
-
-
-def _balanced_workspace(device, n_dst, F, rb):
-    """Tickets + partial-sum slots of cgv_equi_msg_fwd_balanced: zeroed ONCE per (device, stream, shape) -- every launch
-    leaves its tickets at zero.  One workspace serves the launches of one stream (they are ordered); never cached from
-    inside a stream capture (see ``_tail_workspace``: the zero fill would be a captured node that has not run)."""
-    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream), int(n_dst), int(F), int(rb))
-    ws = _BAL_WS.get(key)
-    if ws is None:
-        ws = torch.zeros(int(_lib.load().cgv_equi_msg_balanced_workspace_bytes(int(n_dst), int(F), int(rb))),
-                         dtype=torch.uint8, device=device)
-        if not torch.cuda.is_current_stream_capturing():
-            _BAL_WS[key] = ws
-    return ws
-
-
 # ----------------------------------------------------------------------------- K2 / K4
 class _EquiMessage(torch.autograd.Function):
     """ds, dv of EquiMessageBlock / ContractiveMessageBlock from phi = inv_dense(s)
@@ -114,22 +74,12 @@ class _EquiMessage(torch.autograd.Function):
             dv = v_res.clone() if v_res is not None else torch.zeros(plan.n_dst, F, 3, dtype=_F32, device=phi.device)
         tag = f"equi_msg_fwd:Nd{plan.n_dst}:E{plan.n_edges}:dv{int(with_dv)}"
         grouped = with_dv and _grouped_forward_usable(plan, geom, F, (phi, v, ds, dv, s_res, v_res, bd), Wd)
-        if grouped and options.HOST["fwd_balanced"] and _lib.load().cgv_equi_msg_balanced_supported(F, geom.n_rbf, plan.group_rb):
-            # the same walk over equal edge ranges, one block per CU (K2e): cut groups meet in the workspace
-            ws = _balanced_workspace(phi.device, plan.n_dst, F, plan.group_rb)
-            _lib.call("cgv_equi_msg_fwd_balanced", _lib.ptr(phi), _lib.ptr(v), _lib.ptr(geom.geom_g), _lib.ptr(plan.rowptr_d),
-                      _lib.ptr(plan.src_g), _lib.ptr(plan.dst_g), _lib.ptr(Wd), _lib.ptr(bd), _lib.ptr(ds), _lib.ptr(dv),
-                      plan.n_dst, F, geom.n_rbf, plan.group_rb, plan.n_src, _lib.ptr(s_res), _lib.ptr(v_res),
-                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr(), tag=tag)
-        elif grouped:
-            # shared-source walk: groups of plan.group_rb receivers gather every source row once (K2g), several blocks per
-            # group where its edge range is long enough (their sums meet in the workspace)
-            parts = grouped_parts(plan)
-            ws = _grouped_workspace(phi.device, plan.n_dst, F, plan.group_rb, parts) if parts > 1 else None
-            _lib.call("cgv_equi_msg_fwd_grouped_parts", _lib.ptr(phi), _lib.ptr(v), _lib.ptr(geom.geom_g), _lib.ptr(plan.rowptr_d),
+        if grouped:
+            # shared-source walk: groups of plan.group_rb receivers gather every source row once (K2g)
+            _lib.call("cgv_equi_msg_fwd_grouped", _lib.ptr(phi), _lib.ptr(v), _lib.ptr(geom.geom_g), _lib.ptr(plan.rowptr_d),
                       _lib.ptr(plan.src_g), _lib.ptr(Wd), _lib.ptr(bd), _lib.ptr(ds), _lib.ptr(dv),
                       plan.n_dst, F, geom.n_rbf, plan.group_rb, plan.n_src, plan.n_edges, _lib.ptr(s_res), _lib.ptr(v_res),
-                      parts, _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream_ptr(), tag=tag)
+                      _lib.stream_ptr(), tag=tag)
         else:
             _lib.call("cgv_equi_msg_fwd", _lib.ptr(phi), _lib.ptr(v), _lib.ptr(geom.geom_d), _lib.ptr(plan.rowptr_d),
                       _lib.ptr(plan.src_d), _lib.ptr(Wd), _lib.ptr(bd), _lib.ptr(ds), _lib.ptr(dv), plan.n_dst, F,
@@ -752,25 +702,13 @@ class _UpdateBlockFused(torch.autograd.Function):
         if vt is None or vt.shape != (3 * n, F) or vt.device != dev or not vt.is_contiguous():
             vt = new(3 * n, F)
             _lib.call("cgv_update_rows_from_vec", _lib.ptr(v), _lib.ptr(vt), n, F, st)
-        from .options import HOST
-        # 17 .. 96 bead rows: the norm and the gate in the epilogues of channel-group products (3 launches for 5)
-        fused = (HOST["update_fused_fwd"] and n > 16 and _lib.load().cgv_update_rows_fused_supported(n, F)
-                 and b1 is not None and all(t.data_ptr() % 16 == 0 for t in (vt, Wuv, a0, W1, UV, stack)))
         U_ptr, Vv_ptr = UV.data_ptr(), UV.data_ptr() + 4 * F
-        if fused:
-            _lib.call("cgv_update_uv_norm_fwd_fused", _lib.ptr(vt), _lib.ptr(Wuv), _lib.ptr(s), _lib.ptr(UV), _lib.ptr(stack), n, F, st)
-        else:
-            _dense_fwd(vt, Wuv, None, UV, None, 3 * n, 2 * F, F, 0, st)
-            _lib.call("cgv_update_norm_stack_fwd", _lib.ptr(s), Vv_ptr, _lib.ptr(stack), n, F, 2 * F, st)
+        _dense_fwd(vt, Wuv, None, UV, None, 3 * n, 2 * F, F, 0, st)
+        _lib.call("cgv_update_norm_stack_fwd", _lib.ptr(s), Vv_ptr, _lib.ptr(stack), n, F, 2 * F, st)
         _dense_fwd(stack, W0, b0, a0, z0, n, F, 2 * F, 1, st)
-        if fused:
-            _lib.call("cgv_update_gate_fwd_fused", _lib.ptr(a0), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(UV),
-                      _lib.ptr(s) if residual else None, _lib.ptr(v) if residual else None, _lib.ptr(a), _lib.ptr(ds), _lib.ptr(dv),
-                      n, F, st)
-        else:
-            _dense_fwd(a0, W1, b1, a, None, n, 3 * F, F, 0, st)
-            _lib.call("cgv_update_gate_fwd", U_ptr, Vv_ptr, _lib.ptr(a), _lib.ptr(s) if residual else None,
-                      _lib.ptr(v) if residual else None, _lib.ptr(ds), _lib.ptr(dv), n, F, 2 * F, st)
+        _dense_fwd(a0, W1, b1, a, None, n, 3 * F, F, 0, st)
+        _lib.call("cgv_update_gate_fwd", U_ptr, Vv_ptr, _lib.ptr(a), _lib.ptr(s) if residual else None,
+                  _lib.ptr(v) if residual else None, _lib.ptr(ds), _lib.ptr(dv), n, F, 2 * F, st)
         ctx.save_for_backward(vt, UV, stack, z0, a0, a, W0, W1)
         ctx.params = (u_w, v_w, W0, b0, W1, b1)
         ctx.residual = bool(residual)

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define CGV_VERSION 100 /* 0.1.0 */
+#define CGV_VERSION 101 /* 0.1.1: option numbering changed (18 options) */
 
 #define CGV_E_BADARG (-1)      /* null pointer / negative size */
 #define CGV_E_UNSUPPORTED (-2) /* e.g. n_rbf outside the compiled set */
@@ -65,40 +65,36 @@ const char* cgv_last_error_string(void);
 enum {
   CGV_OPT_MSG_FWD_SPLIT = 0,   /* cgv_equi_msg_fwd: 4 waves share a receiver's segment: -1 auto (>= 16 edges/receiver), 0, 1 */
   CGV_OPT_MSG_BWD_SPLIT = 1,   /* cgv_equi_msg_bwd: waves split a source's segment: -1 auto (>= 48 edges/source), 0, 1 */
-  CGV_OPT_MSG_FWD_KERNEL = 2,  /* cgv_equi_msg_fwd: 0 packed-fp32 VALU kernel (default), 1 MFMA filter-evaluation variant */
-  CGV_OPT_GRP_WAVES = 3,       /* cgv_equi_msg_fwd_grouped: waves per block, 4 (default) or 8 */
-  CGV_OPT_GRP_RECORDS = 4,     /* cgv_equi_msg_fwd_grouped: record stream 0 scalar loads (default), 1 through an LDS ring */
-  CGV_OPT_CSR_BUILD = 5,       /* cgv_csr_build: 0 by rows (default), 1 two-radix-pass construction */
-  CGV_OPT_PSEUDO_CHUNKS = 6,   /* cgv_pseudo_msg_bwd: cap on node chunks, 0 = built-in rule */
-  CGV_OPT_WGRAD_TILING = 7,    /* cgv_wgrad_plan: 0 balanced column tiles (default), 1 widest tile */
-  CGV_OPT_TILE_FWD_LDS_MIN = 8,/* cgv_tile_linear_fwd: minimum 64x64 tile count for the LDS-staged kernels (default 448); 1 = the one-slab
+  CGV_OPT_CSR_BUILD = 2,       /* cgv_csr_build: 0 by rows (default), 1 two-radix-pass construction */
+  CGV_OPT_PSEUDO_CHUNKS = 3,   /* cgv_pseudo_msg_bwd: cap on node chunks, 0 = built-in rule */
+  CGV_OPT_WGRAD_TILING = 4,    /* cgv_wgrad_plan: 0 balanced column tiles (default), 1 widest tile */
+  CGV_OPT_TILE_FWD_LDS_MIN = 5,/* cgv_tile_linear_fwd: minimum 64x64 tile count for the LDS-staged kernels (default 448); 1 = the one-slab
                                   kernel always, 3 = the three-slab ring kernel wherever it is compiled (K = 577..608, 1185..1216) */
-  CGV_OPT_BWD_INPUT_WAVES = 9, /* cgv_tile_linear_bwd_input*: waves per block, 0 = built-in rule */
-  CGV_OPT_PSEUDO_FWD = 10,     /* cgv_pseudo_msg_fwd*: 0 built-in rule; 1..6 = (edges in flight, records staged in LDS) variants; cgv_pseudo_msg_bwd on dense bead graphs: 4 = 8 edges in flight, 5 = records not staged in LDS */
-  CGV_OPT_DECODER_FAT = 11,    /* cgv_decoder_{gate,dense,uv}_bwd: 1 (default) 8-channel blocks where the width allows, 0 always 4 */
-  CGV_OPT_DECODER_WLDS = 12,   /* cgv_decoder_msg_fwd: 1 (default) weight rows by LDS-DMA when they fit in LDS, 0 register path */
-  CGV_OPT_SKINNY_ROWS = 13,    /* cgv_skinny_linear_fwd: row blocks (of 16) per thread block; 0 = built-in rule, 1..4 */
-  CGV_OPT_TILE_FWD_BAL = 14,   /* cgv_tile_linear_fwd: 1 (default) layers of >= 1200 outputs with more than one 32 x 32 tile per CU run as ONE larger register tile per CU where a compiled tile fits (XCD-aware tile order), 0 off, 2 every shape (tests / A-B) */
-  CGV_OPT_OPTIM_ONE_LAUNCH = 15, /* cgv_optim_prepare*: 0 (default) norm pass, then the decision launch; 1 both in ONE launch (the last block decides) -- measured SLOWER on the chignolin step (1.774 against 1.763 ms): 1620 blocks arriving at one device-scope ticket cost more (~12 ns each) than the launch boundary saved; 2: as 0, and cgv_wgrad_gram keeps its separate reduce launch too (A/B: by default the LAST of a problem's eight slice blocks sums them) */
-  CGV_OPT_DECODER_COLSPLIT = 16, /* cgv_decoder_{gate,dense,uv}_bwd: the column tiles of a channel group's backward-input product are split over
+  CGV_OPT_BWD_INPUT_WAVES = 6, /* cgv_tile_linear_bwd_input*: waves per block, 0 = built-in rule */
+  CGV_OPT_PSEUDO_FWD = 7,      /* cgv_pseudo_msg_fwd*: 0 built-in rule; 1..6 = (edges in flight, records staged in LDS) variants; cgv_pseudo_msg_bwd on dense bead graphs: 4 = 8 edges in flight, 5 = records not staged in LDS */
+  CGV_OPT_DECODER_FAT = 8,     /* cgv_decoder_{gate,dense,uv}_bwd: 1 (default) 8-channel blocks where the width allows, 0 always 4 */
+  CGV_OPT_DECODER_WLDS = 9,    /* cgv_decoder_msg_fwd: 1 (default) weight rows by LDS-DMA when they fit in LDS, 0 register path */
+  CGV_OPT_SKINNY_ROWS = 10,    /* cgv_skinny_linear_fwd: row blocks (of 16) per thread block; 0 = built-in rule, 1..4 */
+  CGV_OPT_TILE_FWD_BAL = 11,   /* cgv_tile_linear_fwd: 1 (default) layers of >= 1200 outputs with more than one 32 x 32 tile per CU run as ONE larger register tile per CU where a compiled tile fits (XCD-aware tile order), 0 off, 2 every shape (tests / A-B) */
+  CGV_OPT_OPTIM_ONE_LAUNCH = 12, /* cgv_optim_prepare*: 0 (default) norm pass, then the decision launch; 1 both in ONE launch (the last block decides) -- measured SLOWER on the chignolin step (1.774 against 1.763 ms): 1620 blocks arriving at one device-scope ticket cost more (~12 ns each) than the launch boundary saved; 2: as 0, and cgv_wgrad_gram keeps its separate reduce launch too (A/B: by default the LAST of a problem's eight slice blocks sums them) */
+  CGV_OPT_DECODER_COLSPLIT = 13, /* cgv_decoder_{gate,dense,uv}_bwd: the column tiles of a channel group's backward-input product are split over
                                   several blocks (= CUs; grid y): these products are bound by the fp32 MFMA pipe of ONE CU -- each part repeats the
                                   prologue and writes its own columns of the group's slice.  0 one block per channel group, 1 two, 2 (default) two,
                                   three for uv_bwd (48-row tiles), 3 three everywhere */
-  CGV_OPT_DECODER_NODESPLIT = 17, /* cgv_decoder_uv_fwd (and uv_bwd, see there): 1 (default) 8-channel blocks by node groups of <= 5 nodes (grid y) --
+  CGV_OPT_DECODER_NODESPLIT = 14, /* cgv_decoder_uv_fwd (and uv_bwd, see there): 1 (default) 8-channel blocks by node groups of <= 5 nodes (grid y) --
                                    a third of the MFMAs and of the x rows per block; 0 one 4-channel block over all 3 n rows */
-  CGV_OPT_MSG_FWD_BALANCED = 18, /* cgv_equi_msg_fwd_balanced: four-wave blocks per CU, 3 (default: what the kernel's registers admit, all resident) or 1..4 */
-  CGV_OPT_BWD_INPUT_SPLIT = 19, /* cgv_tile_linear_bwd_input*: few output tiles and a long reduction: -1 (default) 2 - 4 blocks per tile
+  CGV_OPT_BWD_INPUT_SPLIT = 15, /* cgv_tile_linear_bwd_input*: few output tiles and a long reduction: -1 (default) 2 - 4 blocks per tile
                                    when a workspace is registered (cgv_tile_bwd_input_split), 1 never, 2..4 that many */
-  CGV_OPT_MSG_BWD_MFMA = 20,    /* cgv_equi_msg_bwd*, scalar-only upstream: the matrix-core kernel (4 edges per fp32 MFMA, records and
+  CGV_OPT_MSG_BWD_MFMA = 16,    /* cgv_equi_msg_bwd*, scalar-only upstream: the matrix-core kernel (4 edges per fp32 MFMA, records and
                                    rows through vector loads) -1 (default) from 200 edges per node on, 1 wherever it applies
                                    (>= 48 edges per node, n_rbf <= 15, n_feat % 4 == 0), 0 never (the packed-FMA walk) */
-  CGV_OPT_STREAMK = 21,         /* cgv_tile_linear_fwd / cgv_tile_*bwd_input* (and their pair / two-source forms): the LDS-staged stream-K
+  CGV_OPT_STREAMK = 17,         /* cgv_tile_linear_fwd / cgv_tile_*bwd_input* (and their pair / two-source forms): the LDS-staged stream-K
                                    kernel (csrc/streamk_gemm.hip: 128 x 128 tiles, the (tile, 32-deep slab) units of a launch cut into equal
                                    ranges, one block per CU; needs the workspace of cgv_tile_bwd_input_split).  0 (default) where it
                                    wins: single launches of >= 1536 rows with <= 640 outputs over a >= 1200-deep reduction (see
                                    tile_gemm.hip: sk_wanted); 1 never; 2 / 3 wherever the operands allow, with one / two blocks per CU
                                    (tests, A-B); >= 16: a grid of exactly that many blocks (experiments) */
-  CGV_OPT_COUNT = 22
+  CGV_OPT_COUNT = 18
 };
 /* Measurement: store the GPU wall clock (cgv_timestamp_hz ticks per second) into *slot, in stream order; capturable. */
 int cgv_timestamp(uint64_t* slot /*device*/, void* stream);
@@ -292,38 +288,11 @@ int cgv_equi_msg_fwd_grouped(const float* phi /*[Ns,3F]*/, const float* v /*[Ns,
                              float* dv /*[Nd,F,3]*/, int n_dst, int n_feat, int n_rbf, int rb, int64_t n_rows,
                              int64_t n_edges /* records in geom_g */, const float* s_res /*[Nd,F] or NULL*/, const float* v_res /*[Nd,F,3] or NULL*/,
                              void* stream);
-/* cgv_equi_msg_fwd_grouped with `parts` (1..4) blocks per (group, channel tile): the group's edge range is cut into
- * parts x 4 wave slices instead of 4 -- shorter blocks in larger number, which the dispatcher spreads evenly over the CUs
- * where one block per item gives 3.25 blocks per CU (chignolin graph: a quarter of the CUs carry a fourth block) or
- * blocks that live 20-145 us depending on their group's degree (2000-atom graph: the launch ends with a few long ones).
- * The parts' sums meet in the workspace: every block leaves its own in its slot, the block that draws the group's last
- * ticket adds the slots in part order and stores -- results do not depend on timing.  rb = 2, default kernel only
- * (otherwise parts is taken as 1).  workspace: cgv_equi_msg_grouped_workspace_bytes bytes, 16-byte aligned, ZERO-FILLED
- * once by the caller (self-resetting tickets at its head); one workspace serves the launches of one stream. */
-size_t cgv_equi_msg_grouped_workspace_bytes(int n_dst, int n_feat, int rb, int parts);
-int cgv_equi_msg_fwd_grouped_parts(const float* phi /*[Ns,3F]*/, const float* v /*[Ns,F,3]*/, const float* geom_g,
-                                   const int32_t* rowptr_d, const int32_t* src_g,
-                                   const float* Wd /*[3F,R]*/, const float* bd /*[3F]*/, float* ds /*[Nd,F]*/,
-                                   float* dv /*[Nd,F,3]*/, int n_dst, int n_feat, int n_rbf, int rb, int64_t n_rows,
-                                   int64_t n_edges, const float* s_res /*[Nd,F] or NULL*/,
-                                   const float* v_res /*[Nd,F,3] or NULL*/, int parts, void* workspace,
-                                   size_t workspace_bytes, void* stream);
-/* The same shared-source walk with the work cut into EQUAL EDGE RANGES instead of (group, channel tile) blocks:
- * every wave walks the same number of edges of its channel tile's group-ordered edge array, whatever the groups'
- * sizes, on a grid that is resident at once (cgv_equi_msg_fwd_grouped: 3.25 blocks per CU on the chignolin graph, block lifetimes 20-145 us on the 2000-atom
- * graph).  A group cut by a range boundary is finished by the last contributing wave to arrive, which adds the
- * contributors' partial sums (workspace) in range order: results do not depend on timing.  rb = 2 only; dst_g = the
- * plan's receiver ids in group order.  The edge count is read from rowptr_d[n_dst] on the device.
- * workspace: cgv_equi_msg_balanced_workspace_bytes bytes, 16-byte aligned, ZERO-FILLED once by the caller (its head holds
- * self-resetting tickets); one workspace serves every launch of one stream, launches on concurrent streams need their own. */
-int cgv_equi_msg_balanced_supported(int n_feat, int n_rbf, int rb);   /* even n_feat / n_rbf, rb = 2 */
-size_t cgv_equi_msg_balanced_workspace_bytes(int n_dst, int n_feat, int rb);
-int cgv_equi_msg_fwd_balanced(const float* phi /*[Ns,3F]*/, const float* v /*[Ns,F,3]*/, const float* geom_g,
-                              const int32_t* rowptr_d, const int32_t* src_g, const int32_t* dst_g,
-                              const float* Wd /*[3F,R]*/, const float* bd /*[3F]*/, float* ds /*[Nd,F]*/,
-                              float* dv /*[Nd,F,3]*/, int n_dst, int n_feat, int n_rbf, int rb, int64_t n_rows,
-                              const float* s_res /*[Nd,F] or NULL*/, const float* v_res /*[Nd,F,3] or NULL*/,
-                              void* workspace, size_t workspace_bytes, void* stream);
+/* Removed after losing their A/B against the launch above (commit 028bd3e last held them; DESIGN.md 8,
+ * profiles/r05_k2_parts_ab.txt, profiles/r05_k2e_*): 2-4 blocks per (group, channel tile) whose sums met in a workspace
+ * (level or slower on all three workloads), the walk cut into equal edge ranges on a resident grid (chignolin 45.6
+ * against 42.7 us, 2000 atoms 678 against 600), 8-wave blocks (942 against 654 us), the record stream through an LDS ring,
+ * and a matrix-core filter evaluation in cgv_equi_msg_fwd (71 against 55 us). */
 /* Backward.  gs / gv are the upstream gradients at the receivers (gv == NULL when dv is not
  * consumed).  Traverses the src-sorted view; writes g_phi [Ns,3F], g_v [Ns,F,3] (only if gv),
  * gWd [3F,R], gbd [3F] completely (zeros where nothing flows).  Deterministic two-stage
@@ -466,17 +435,9 @@ int cgv_decoder_dense_fwd(const float* x, const float* W /*[N,K]*/, const float*
 int cgv_decoder_uv_fwd(const float* rows, const float* Wuv, float* UV, float* stack, int n_nodes, int n_feat, void* stream);
 int cgv_decoder_gate_fwd(const float* a0, const float* W1p, const float* b1p, const float* UV, const float* stack,
                          const float* v2, float* a, float* s3, float* v3, int n_nodes, int n_feat, void* stream);
-/* UpdateBlock forward (conv.py:593-616) with the element-wise halves in the products' epilogues, for 1..96 bead rows -- the
- * per-block path beyond the channel-group decoder's 16 nodes (cgv_update_rows_fused_supported):
- *   uv_norm   UV [3n, 2F] = rows [u_mat; v_mat]^T ; stack [n, 2F] = [s | sqrt(sum_xyz (Vv^2 + 1e-10))]   (s NULL: first half untouched)
- *   gate      a [n, 3F] = a0 W1^T + b1 ; s_out = (U.Vv) a_sv + a_ss (+ s_res) ; v_out = U a_vv (+ v_res)  (residual adds of
- *             cgvae.py:122-123 when s_res / v_res are given)
- * replacing cgv_skinny / tile_linear_fwd + cgv_update_norm_stack_fwd and + cgv_update_gate_fwd (two launches each). */
-int cgv_update_rows_fused_supported(int n_rows, int n_feat);
-int cgv_update_uv_norm_fwd_fused(const float* rows, const float* Wuv /*[2F, F]*/, const float* s /*or NULL*/, float* UV, float* stack,
-                                 int n_nodes, int n_feat, void* stream);
-int cgv_update_gate_fwd_fused(const float* a0, const float* W1 /*[3F, F]*/, const float* b1, const float* UV, const float* s_res /*or NULL*/,
-                              const float* v_res /*or NULL*/, float* a, float* s_out, float* v_out, int n_rows, int n_feat, void* stream);
+/* (A forward of the UpdateBlock with both element-wise halves in channel-group epilogues, for 17..96 bead rows, measured
+ * slower than product + element-wise launch on the dipeptide and the 2000-atom graph and was removed; commit 028bd3e last
+ * held it.) */
 int cgv_decoder_gate_bwd(const float* UV, const float* a, const float* gs_base /*or NULL*/, const float* gs_slices /*or NULL*/,
                          int gs_n_slices, int64_t gs_slice_stride, const float* gv /*or NULL*/, const float* W1p, float* ga,
                          float* gUV, float* gs_sum, float* slices_out, int64_t out_slice_stride, int n_nodes, int n_feat,

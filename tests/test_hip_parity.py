@@ -624,16 +624,15 @@ def test_dense_with_fused_swish_vs_fp64(M, F):
     assert_close(dense.bias.grad, bd_.grad, "gb", 3e-6)
 
 
-@pytest.mark.parametrize("n,F,fused_fwd", [(12, 600, 0), (96, 600, 0), (64, 128, 0), (96, 600, 1), (64, 128, 1), (37, 200, 1), (17, 64, 1)])
-def test_fused_update_block_equals_composition(n, F, fused_fwd, options):
+@pytest.mark.parametrize("n,F", [pytest.param(12, 600, id="12-600-0"), pytest.param(96, 600, id="96-600-0"),
+                                 pytest.param(64, 128, id="64-128-0")])      # (ids: as before the fused-forward legs left)
+def test_fused_update_block_equals_composition(n, F):
     """The single-node UpdateBlock path (arena-managed parameters, merged [u_mat; v_mat] product, grouped
     weight gradients) against the tensor-op composition and the fp64 oracle formulas; 12 beads run on the skinny
-    kernels, 64 / 96 beads (3n = 192 / 288 rows) on the tile kernels."""
+    kernels, 64 / 96 beads (3n = 192 / 288 rows) on the tile kernels; the norm / gate are element-wise launches behind
+    the products."""
     from coarsegrainingvae_amd.trainer import ParamArena
     from coarsegrainingvae_amd.ops import _UpdateBlockFused
-    # fused_fwd: beyond 16 rows the norm / gate run in the epilogues of channel-group products (cgv_update_*_fwd_fused,
-    # round 5) or, with 0, as element-wise launches behind the tile / skinny products (rounds 2-4)
-    options.set("update_fused_fwd", fused_fwd)
     torch.manual_seed(3)
     blk = cg.UpdateBlock(F, "swish", 0.0).to(DEV)
     with torch.no_grad():
@@ -788,19 +787,6 @@ def test_batched_radius_graph_dataset_path():
         assert torch.equal(ds.props["CG_nbr_list"][k], O.get_neighbor_list(props["CG_nxyz"][k][:, 1:4], 9.5, True))
     ds.generate_neighbor_list(4.0, None, device=DEV)                 # --cg_radius_graph: bead graph from bonds
     assert ds.props["CG_nbr_list"][0].shape[1] == 2
-
-
-@pytest.mark.parametrize("F,R", [(7, 8), (24, 10), (129, 10), (600, 10), (66, 16), (34, 20), (20, 4)])
-@pytest.mark.parametrize("with_gv", [True, False])
-def test_equi_message_matrix_core_forward(F, R, with_gv, options):
-    """The MFMA variant of the fused forward, forced on (CGV_OPT_MSG_FWD_KERNEL is an A/B switch of the launcher)."""
-    options.set("msg_fwd_kernel", 1)
-    gen = torch.Generator().manual_seed(F * 3 + R)
-    n = 40
-    xyz = torch.rand(n, 3, generator=gen) * 4.0
-    nbrs, _ = O.make_directed(O.get_neighbor_list(xyz, 3.2, True))
-    nbrs = torch.cat([nbrs, torch.tensor([[5, 2], [5, 3], [5, 2]])])          # asymmetric extras, a duplicate
-    _block_vs_oracle(F, R, n, nbrs, xyz, with_gv, seed=F + R)
 
 
 def test_equi_message_high_degree_split_path():
@@ -1116,17 +1102,15 @@ def test_shared_source_forward_matches_fp64_and_plain_kernel(F, R, n, box, cut, 
         assert_close(x.grad, y.grad, "grad " + name, 1e-6)
 
 
-@pytest.mark.parametrize("wpb", [3, 2])
 @pytest.mark.parametrize("F,R,n,kind", [(600, 10, 83, "dense"), (600, 10, 332, "dense"), (130, 6, 41, "holes"), (24, 8, 10, "tiny"),
                                         (256, 10, 64, "one_edge"), (64, 8, 29, "holes"), (600, 10, 200, "hub")])
-def test_balanced_forward_ranges_cut_groups_anywhere(F, R, n, kind, wpb, options):
-    """K2e (cgv_equi_msg_fwd_balanced): equal edge ranges per wave whatever the groups' sizes.  Against fp64 and, bit for
-    bit, against itself over repeated launches (the tickets reset themselves; the sum order of a cut group is the range
-    order, not the arrival order).  Graphs: dense; receivers without edges ahead of, between and behind the others;
-    fewer edges than ranges (most waves idle, every group cut or whole at random); one edge; one hub receiver holding
-    most edges (its group spans hundreds of ranges)."""
-    from coarsegrainingvae_amd import ops
-    gen = torch.Generator().manual_seed(F + n + wpb)
+def test_grouped_forward_on_awkward_graphs(F, R, n, kind):
+    """K2g (cgv_equi_msg_fwd_grouped, called directly: one block per (group of 2 receivers, channel tile), its four waves
+    on quarters of the group's edge range).  Against fp64 and, bit for bit, against itself over repeated launches.
+    Graphs: dense; receivers without edges ahead of, between and behind the others; seven edges (most waves idle); one
+    edge; one hub receiver holding most edges (8000 terms per sum)."""
+    _lib = cg._lib
+    gen = torch.Generator().manual_seed(F + n + 3)
     xyz = torch.rand(n, 3, generator=gen) * 5.0
     if kind == "dense":
         nbrs, _ = O.make_directed(O.get_neighbor_list(xyz, 9.0, True))
@@ -1152,13 +1136,21 @@ def test_balanced_forward_ranges_cut_groups_anywhere(F, R, n, kind, wpb, options
     ds64, dv64 = _equi_message_fp64(phi, v, Wd, bd, geom.geom_g[:E].cpu(), plan.dst_g[:E].cpu().long(),
                                     plan.src_g[:E].cpu().long(), R, geom.group_unit_offset, n)
     args = [x.to(DEV) for x in (phi, v, Wd, bd)]
-    options.set("msg_fwd_balanced", wpb)
-    options.set("fwd_balanced", 1)
-    ds, dv = ops.equi_message(*args, plan, geom, True)
+    assert _lib.load().cgv_equi_msg_grouped_supported(F, R, 2)
+
+    def grouped(s_r=None, v_r=None):
+        ds = torch.full((n, F), float("nan"), device=DEV)       # every receiver is written, the edgeless ones too
+        dv = torch.full((n, F, 3), float("nan"), device=DEV)
+        _lib.call("cgv_equi_msg_fwd_grouped", *map(_lib.ptr, args[:2]), _lib.ptr(geom.geom_g), _lib.ptr(plan.rowptr_d),
+                  _lib.ptr(plan.src_g), *map(_lib.ptr, args[2:]), _lib.ptr(ds), _lib.ptr(dv), n, F, R, 2, n, E,
+                  _lib.ptr(s_r), _lib.ptr(v_r), _lib.stream_ptr())
+        return ds, dv
+
+    ds, dv = grouped()
     tol = 2e-6 if kind != "hub" else 2e-5                      # (8000 terms per sum on the hub)
     assert_close(ds, ds64, "ds vs fp64", tol)
     assert_close(dv, dv64, "dv vs fp64", tol)
-    ds_r, dv_r = ops.equi_message(*args, plan, geom, True, s_res.to(DEV), v_res.to(DEV))
+    ds_r, dv_r = grouped(s_res.to(DEV), v_res.to(DEV))
     assert_close(ds_r, ds64 + s_res.double(), "residual s", tol)
     assert_close(dv_r, dv64 + v_res.double(), "residual v", tol)
     deg = torch.bincount(plan.dst_g[:E].cpu().long(), minlength=n)
@@ -1166,21 +1158,8 @@ def test_balanced_forward_ranges_cut_groups_anywhere(F, R, n, kind, wpb, options
         assert float(ds[i].abs().max()) == 0.0 and float(dv[i].abs().max()) == 0.0
         assert torch.equal(ds_r[i].cpu(), s_res[i]) and torch.equal(dv_r[i].cpu(), v_res[i])
     for _ in range(5):                                          # repeated launches: same bits
-        ds2, dv2 = ops.equi_message(*args, plan, geom, True)
+        ds2, dv2 = grouped()
         assert torch.equal(ds2, ds) and torch.equal(dv2, dv)
-    options.set("fwd_balanced", 0)                              # the per-group kernel on the same plan
-    ds_g, dv_g = ops.equi_message(*args, plan, geom, True)
-    assert_close(ds, ds_g, "ds vs per-group kernel", tol)
-    assert_close(dv, dv_g, "dv vs per-group kernel", tol)
-    # ... and with 2 - 4 blocks per (group, channel tile) whose sums meet in the workspace (cgv_equi_msg_fwd_grouped_parts)
-    for parts in (2, 3, 4):
-        options.set("fwd_parts", parts)
-        ds_p, dv_p = ops.equi_message(*args, plan, geom, True, s_res.to(DEV), v_res.to(DEV))
-        assert_close(ds_p, ds64 + s_res.double(), f"{parts} parts: residual s", tol)
-        assert_close(dv_p, dv64 + v_res.double(), f"{parts} parts: residual v", tol)
-        for _ in range(3):
-            ds_q, dv_q = ops.equi_message(*args, plan, geom, True, s_res.to(DEV), v_res.to(DEV))
-            assert torch.equal(ds_q, ds_p) and torch.equal(dv_q, dv_p)
 
 
 def test_batch_graph_uses_receiver_groups_on_dense_atom_graphs(options):
