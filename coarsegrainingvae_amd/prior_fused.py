@@ -10,7 +10,9 @@ their rows of ``inv_dense.1`` get explicit zero gradients, exactly what autograd
 channel is still COMPUTED forward unless the explicit ``with_dv = False`` option says otherwise.
 
 Used for bead graphs of at most 16 nodes when every parameter is arena-managed (under ``Trainer`` from the second step
-on); ``tests/test_hip_parity.py::test_fused_prior_loop_equals_per_block_path`` compares it with the per-block path.
+on); ``tests/test_hip_parity.py::test_fused_prior_loop_equals_per_block_path`` compares it with the per-block path,
+``tests/test_prior_loop_fp64.py`` compares both, tensor by tensor and on every kernel path, with a float64 reference of the
+loop, and the forward kernel's vector channel (which never leaves this node) with the same reference by direct call.
 """
 from __future__ import annotations
 
