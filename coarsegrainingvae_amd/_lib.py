@@ -238,6 +238,14 @@ PROTOTYPES = {
     "cgv_hbond_chunk": (_i, []),
     "cgv_hbond_workspace_bytes": (_sz, [_i, _i, _i]),
     "cgv_hbond_counts": (_i, [_p] * 6 + [_i, _i, _i, _i, _f, _f] + [_p] * 5 + [_p, _sz, _p]),
+    "cgv_lddt_max_atoms": (_i, []),
+    "cgv_lddt_max_structures": (_i, []),
+    "cgv_lddt_max_references": (_i, []),
+    "cgv_lddt_row_tile": (_i, []),
+    "cgv_lddt_col_tile": (_i, []),
+    "cgv_lddt_chunk": (_i, []),
+    "cgv_lddt_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_lddt_counts": (_i, [_p] * 7 + [_i] * 4 + [_f] * 6 + [_p] * 3 + [_p, _sz, _p]),
     "cgv_dssp_max_residues": (_i, []),
     "cgv_dssp_max_structures": (_i, []),
     "cgv_dssp_wave_path_max": (_i, []),

@@ -1,5 +1,5 @@
 // What the pair kernels that stream a packed copy [S, P] float4 of every structure share (K20 contact_map.hip, K25
-// hbond.hip): the rule that cuts the structure axis into slices, and the per-structure counters of the chunk of structures a
+// hbond.hip, K28 lddt.hip): the rule that cuts the structure axis into slices, and the per-structure counters of the chunk of structures a
 // block stages at a time.  Only integers here, but EVERY FILE THAT INCLUDES THIS IS COMPILED WITH -ffp-contract=off
 // (build.py: SOURCE_FLAGS): the predicates beside it are restated on the host bit for bit.
 #pragma once
@@ -34,6 +34,20 @@ struct ChunkHits {
     if (tid < 2 * CHUNK) {
       const int which = tid / CHUNK, sl = tid % CHUNK, v = hits[which][sl];
       if (v != 0 && s0 + sl < s_end) atomicAdd((which ? n_native : n_all) + s0 + sl, v);
+    }
+  }
+};
+
+// ChunkHits' sibling for a kernel with N counters per structure, laid out as the caller's table [S, N] (K28 lddt.hip: N = 6)
+template <int CHUNK, int N>
+struct ChunkCounts {
+  int v[CHUNK][N];
+  __device__ __forceinline__ void zero(int tid) { if (tid < CHUNK * N) v[tid / N][tid % N] = 0; }
+  __device__ __forceinline__ void add(int sl, int k, int x) { atomicAdd(&v[sl][k], x); }
+  __device__ __forceinline__ void flush(int s0, int s_end, int tid, int* __restrict__ table) {
+    if (tid < CHUNK * N) {
+      const int sl = tid / N, k = tid % N, x = v[sl][k];
+      if (x != 0 && s0 + sl < s_end) atomicAdd(table + (size_t)(s0 + sl) * N + k, x);
     }
   }
 };

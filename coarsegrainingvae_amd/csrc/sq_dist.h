@@ -8,6 +8,7 @@
 //   K25 hbond.hip                                    sq_dist2 against a cutoff, and a rounded dot product beside it
 //   K26 dssp.hip                                     sq_dist2 beside its rounded reciprocal distances
 //   K27 pca.hip (through gram_dev.h)                 sq_wave_sum(double) alone; its own fp64 feature needs the flag as well
+//   K28 lddt.hip                                     sqrtf(sq_dist2) of a model against that of its reference; the wave sum
 // packed_dev.h and gram_dev.h stand on the same contract.
 #pragma once
 #include "cgv_common.h"

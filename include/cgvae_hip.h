@@ -1523,6 +1523,65 @@ int cgv_pca_project(const float* y, const int32_t* sel /*[m]*/, const double* ce
                     double* proj /*[n_structures,k]*/, int comp_a, int comp_b, int n_bins2, double lo_a, double hi_a, double lo_b,
                     double hi_b, int32_t* counts, int32_t* outside, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K28  local distance difference test (lDDT, Mariani et al. 2013) and steric clashes of an ensemble -- how well every model
+ * structure keeps the local distances of the reference structure it is scored against, WITHOUT superposition, per structure
+ * and per atom, and how many pairs of non-bonded atoms overlap.  Nothing in the reference computes it.  Lengths in Angstrom.
+ *   xyz [n_structures,n_atoms,3] fp32         the model structures
+ *   ref_xyz [n_references,n_atoms,3] fp32     the reference structures
+ *   ref_index [n_structures] int32, HOST      the reference of every model structure, in [0, n_references): checked here,
+ *                                             then copied to the workspace on `stream` (the only host array of this header's
+ *                                             analysis entry points; the caller renumbers it per launch anyway)
+ *   sel [m] int32                             the selected atoms.  An index outside [0, n_atoms) reads atom 0 (the host
+ *                                             wrapper refuses such tables); nothing is read out of bounds.
+ *   excl_lddt, excl_clash [m,W] uint32, W = ceil(m / 32): bit (j & 31) of word j >> 5 of row i: the pair (i, j) never counts
+ *                                             for the distance test / as a clash.  SYMMETRIC (the caller's duty: the
+ *                                             per-atom counts walk ordered pairs); the diagonal never counts whatever the
+ *                                             masks say; bits past m are ignored.
+ *   radii [m] fp32                            of the selected atoms, for the clash test
+ * For an unordered pair {i, j}, i != j, in fp32 with every operation individually rounded (no fma; sqrtf correctly rounded):
+ *   q0 = sq_dist2(ref_i, ref_j), q = sq_dist2(x_i, x_j)      ((dx*dx + dy*dy) + dz*dz, csrc/sq_dist.h)
+ *   included     iff  not excl_lddt  and  q0 < radius2       radius2: the CALLER's fp32(R0) * fp32(R0)
+ *   e = fabsf(sqrtf(q) - sqrtf(q0))                          one rounded subtraction
+ *   preserved_k  iff  included  and  e < t_k                 k = 0 .. 3, t0 < t1 < t2 < t3
+ *   c = (r_i + r_j) - tolerance
+ *   clash        iff  not excl_clash  and  c > 0  and  q < c * c
+ * Every comparison is strict and false for a NaN.  A host that restates the arithmetic gets every integer below exactly; no
+ * floating-point result leaves the device.  The six quantities, in this order: included, preserved_0 .. preserved_3, clash.
+ *   struct_counts [n_structures,6] int32      overwritten: the six quantities of a structure over its pairs i < j
+ *   atom_counts [m,6] int64                   ADDED to: the six quantities of selected atom i over the pairs {i, j} that
+ *                                             contain it, summed over the good structures of this call; a caller cuts a long
+ *                                             ensemble into launches and zeroes it once.  Over good structures
+ *                                             sum_i atom_counts[i] = 2 sum_s struct_counts[s].
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate in a selected
+ *                                             atom, and for one whose reference has one.  Its struct_counts are -1, it
+ *                                             enters no sum.  Atoms outside the selection are not looked at.
+ * Launches: one wave per structure gathers the selection into a packed float4 copy in the workspace, first of the references
+ *   (with a flag per reference), then of the models (bad, struct_counts = 0 or -1); then grid (column tiles of
+ *   cgv_lddt_col_tile(), row tiles of cgv_lddt_row_tile(), slices of the structure axis) x 256 threads over the full grid of
+ *   ordered pairs: a lane owns a row and the 32 columns of its wave, the row's six counters stay in registers;
+ *   cgv_lddt_chunk() structures at a time go through LDS; sqrtf(q0) and the inclusion word of a thread's pairs stay in
+ *   registers while ref_index does not change between consecutive good structures.  Per-structure counts take the pairs
+ *   above the diagonal.  Integer sums meet in atomicAdd: the same bits on every call, however the structures are cut.
+ * workspace: cgv_lddt_workspace_bytes(n_structures, n_references, m) bytes (0 beyond a limit), 16-byte aligned, contents
+ *   need not survive.
+ * Limits: 1 <= m <= cgv_lddt_max_atoms(), n_structures <= cgv_lddt_max_structures() and n_references <=
+ *   cgv_lddt_max_references() per launch.  Beyond a limit, for a ref_index outside [0, n_references), for a radius2,
+ *   threshold or tolerance that is not a finite number >= 0 and for thresholds that are not ascending the call fails
+ *   (CGV_E_BADARG) with its reason before any launch; n_structures = 0 returns 0 and does nothing.  See DESIGN.md (K28 row). */
+int cgv_lddt_max_atoms(void);
+int cgv_lddt_max_structures(void);
+int cgv_lddt_max_references(void);
+int cgv_lddt_row_tile(void);
+int cgv_lddt_col_tile(void);
+int cgv_lddt_chunk(void);
+size_t cgv_lddt_workspace_bytes(int n_structures, int n_references, int m);
+int cgv_lddt_counts(const float* xyz, const float* ref_xyz, const int32_t* ref_index /*[S], host*/, const int32_t* sel /*[m]*/,
+                    const uint32_t* excl_lddt /*[m,W]*/, const uint32_t* excl_clash /*[m,W]*/, const float* radii /*[m]*/,
+                    int n_structures, int n_references, int n_atoms, int m, float radius2, float t0, float t1, float t2, float t3,
+                    float tolerance, int32_t* struct_counts /*[S,6]*/, int64_t* atom_counts /*[m,6]*/, int32_t* bad /*[S]*/,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
