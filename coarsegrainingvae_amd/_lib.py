@@ -260,6 +260,15 @@ PROTOTYPES = {
     "cgv_pca_moments_workspace_bytes": (_sz, [_i, _i]),
     "cgv_pca_moments": (_i, [_p] * 4 + [_i] * 3 + [_p] * 3 + [_p, _sz, _p]),
     "cgv_pca_project": (_i, [_p] * 6 + [_i] * 4 + [_p, _i, _i, _i] + [C.c_double] * 4 + [_p] * 3),
+    "cgv_pairdist_max_atoms": (_i, []),
+    "cgv_pairdist_max_structures": (_i, []),
+    "cgv_pairdist_max_classes": (_i, []),
+    "cgv_pairdist_max_bins": (_i, []),
+    "cgv_pairdist_row_tile": (_i, []),
+    "cgv_pairdist_col_tile": (_i, []),
+    "cgv_pairdist_chunk": (_i, []),
+    "cgv_pairdist_workspace_bytes": (_sz, [_i, _i]),
+    "cgv_pairdist_counts": (_i, [_p] * 4 + [_i] * 5 + [_f] * 2 + [_p] * 3 + [_p, _sz, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

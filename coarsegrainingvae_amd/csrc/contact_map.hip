@@ -83,15 +83,13 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
   __shared__ float4 st[CT_CHUNK][CT_ROWS + CT_COLS];
   __shared__ ChunkHits<CT_CHUNK> hits;
   const int r0 = (int)blockIdx.y * CT_ROWS, c0 = (int)blockIdx.x * CT_COLS;
-  if (c0 + CT_COLS - 1 <= r0) return;                        // no column of the tile is above a row of it
+  if (!upper_tile_live(r0, c0, CT_COLS)) return;             // no column of the tile is above a row of it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = r0 + lane, cb = c0 + 32 * wave;            // this thread's row and the first of its 32 columns
   // bit u: the pair (row, cb + u) is this thread's to count -- inside the selection, above the diagonal, not excluded
   uint32_t ok = 0, nat = 0;
   if (row < m && cb < m) {
-    const uint32_t inside = m - cb >= 32 ? 0xffffffffu : (1u << (m - cb)) - 1u;
-    const uint32_t above = row < cb ? 0xffffffffu : row >= cb + 31 ? 0u : 0xffffffffu << (row - cb + 1);
-    ok = inside & above & ~excl[(size_t)row * words + (cb >> 5)];
+    ok = upper_pair_word(row, cb, m) & ~excl[(size_t)row * words + (cb >> 5)];
     if (native != nullptr) nat = ok & native[(size_t)row * words + (cb >> 5)];
   }
   const bool wave_live = __any(ok != 0) != 0;
@@ -235,10 +233,8 @@ int cgv_contact_counts(const float* xyz, const int32_t* sel, const uint32_t* exc
   int rc = cgv::check_launch("cgv_contact_counts (preparation)");
   if (rc || m < 2) return rc;
   const int nr = (m + cgv::CT_ROWS - 1) / cgv::CT_ROWS, nc = (m + cgv::CT_COLS - 1) / cgv::CT_COLS;
-  int live = 0;                                              // tiles that hold a pair i < j
-  for (int r = 0; r < nr; ++r) live += nc - (r >> 1);
   int per;
-  const int slices = cgv::struct_slices(n_structures, live, cgv::CT_CHUNK, &per);
+  const int slices = cgv::struct_slices(n_structures, cgv::upper_live_tiles(nr, nc, cgv::CT_ROWS, cgv::CT_COLS), cgv::CT_CHUNK, &per);
   hipLaunchKernelGGL(cgv::contact_pairs_k, dim3((unsigned)nc, (unsigned)nr, (unsigned)slices), dim3(256), 0, st, packed, excluded,
                      native, n_structures, m, (m + 31) / 32, per, cutoff2, counts, n_contacts, n_native);
   return cgv::check_launch("cgv_contact_counts");

@@ -1582,6 +1582,56 @@ int cgv_lddt_counts(const float* xyz, const float* ref_xyz, const int32_t* ref_i
                     float tolerance, int32_t* struct_counts /*[S,6]*/, int64_t* atom_counts /*[m,6]*/, int32_t* bad /*[S]*/,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K29  pair-distance distributions of an ensemble -- over the structures of a call, the histogram of the distances between
+ * the pairs of selected atoms, one histogram per unordered pair of atom classes: the radial / pair distribution P(r).
+ * Nothing in the reference computes it.  Lengths in Angstrom.
+ *   xyz [n_structures,n_atoms,3] fp32         the structures
+ *   sel [m] int32                             the selected atoms.  An index outside [0, n_atoms) reads atom 0 (the host
+ *                                             wrapper refuses such tables); nothing is read out of bounds.
+ *   cls [m] int32                             the class of every selected atom, in [0, n_classes); a value outside counts as
+ *                                             class 0 (the host wrapper refuses such tables).  The unordered class pair
+ *                                             (a <= b) has the index a * C - a * (a - 1) / 2 + (b - a), C = n_classes:
+ *                                             P = C (C + 1) / 2 of them.
+ *   excluded [m,W] uint32, W = ceil(m / 32)   bit (j & 31) of word j >> 5 of row i: the pair (i, j) never counts.  Only the
+ *                                             bits j > i are read; the diagonal never counts; bits past m are ignored.
+ * For a pair i < j that is not excluded, in fp32 with every operation individually rounded (no fma; sqrtf correctly rounded):
+ *   q = sq_dist2(x_i, x_j)                    ((dx*dx + dy*dy) + dz*dz, csrc/sq_dist.h)
+ *   in range  iff  q < rmax2                  strict, false for a NaN; rmax2: the CALLER's fp32(r_max) * fp32(r_max)
+ *   b = min((int)(sqrtf(q) * scale), n_bins - 1)        scale: the CALLER's fp32(n_bins / fp32(r_max)), the quotient in fp64
+ * A host that restates the arithmetic gets every integer below exactly; no floating-point result leaves the device.
+ *   hist [P,n_bins] int64                     ADDED to: the in-range pairs of the good structures of this call, by class pair
+ *                                             and bin; a caller cuts a long ensemble into launches and zeroes it once
+ *   beyond [P] int64                          ADDED to: the pairs with q >= rmax2, by class pair.  For every class pair
+ *                                             sum_b hist[p][b] + beyond[p] = good structures x its non-excluded pairs i < j.
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate in a selected
+ *                                             atom; it enters no sum.  Atoms outside the selection are not looked at.
+ * Launches: one wave per structure gathers the selection into a packed float4 copy in the workspace and decides bad; then
+ *   grid (column tiles of cgv_pairdist_col_tile(), row tiles of cgv_pairdist_row_tile(), slices of the structure axis) x 256
+ *   threads over the tiles that hold a pair i < j: a lane owns a row and the 32 columns of its wave; cgv_pairdist_chunk()
+ *   structures at a time go through LDS; the block's histogram is private in LDS (32-bit counters, integer LDS atomics; as
+ *   many as four copies, chosen by lane, where they fit 64 KB with the staging; the pairs beyond r_max are counted in
+ *   registers first) and is added to hist / beyond once, one 64-bit atomicAdd per nonzero counter.  A block counts at most 2^13 pairs x 2^18 structures = 2^31: no 32-bit counter wraps.  Integer sums meet
+ *   in atomicAdd: the same bits on every call, however the structures are cut.
+ * workspace: cgv_pairdist_workspace_bytes(n_structures, m) bytes (0 beyond a limit), 16-byte aligned, contents need not
+ *   survive.
+ * Limits: 1 <= m <= cgv_pairdist_max_atoms(), n_structures <= cgv_pairdist_max_structures() per launch, 1 <= n_classes <=
+ *   cgv_pairdist_max_classes(), 1 <= n_bins <= cgv_pairdist_max_bins().  Beyond a limit, for an rmax2 that is not a finite
+ *   number >= 0 and for a scale that is not a finite number > 0 the call fails (CGV_E_BADARG) with its reason before any
+ *   launch and writes nothing; n_structures = 0 returns 0 and does nothing.  See DESIGN.md (PD row). */
+int cgv_pairdist_max_atoms(void);
+int cgv_pairdist_max_structures(void);
+int cgv_pairdist_max_classes(void);
+int cgv_pairdist_max_bins(void);
+int cgv_pairdist_row_tile(void);
+int cgv_pairdist_col_tile(void);
+int cgv_pairdist_chunk(void);
+size_t cgv_pairdist_workspace_bytes(int n_structures, int m);
+int cgv_pairdist_counts(const float* xyz, const int32_t* sel /*[m]*/, const int32_t* cls /*[m]*/, const uint32_t* excluded /*[m,W]*/,
+                        int n_structures, int n_atoms, int m, int n_classes, int n_bins, float rmax2, float scale,
+                        int64_t* hist /*[P,n_bins]*/, int64_t* beyond /*[P]*/, int32_t* bad /*[S]*/, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
