@@ -269,6 +269,14 @@ PROTOTYPES = {
     "cgv_pairdist_chunk": (_i, []),
     "cgv_pairdist_workspace_bytes": (_sz, [_i, _i]),
     "cgv_pairdist_counts": (_i, [_p] * 4 + [_i] * 5 + [_f] * 2 + [_p] * 3 + [_p, _sz, _p]),
+    "cgv_dist_moments_max_atoms": (_i, []),
+    "cgv_dist_moments_max_structures": (_i, []),
+    "cgv_dist_moments_max_total": (_i, []),
+    "cgv_dist_moments_row_tile": (_i, []),
+    "cgv_dist_moments_col_tile": (_i, []),
+    "cgv_dist_moments_chunk": (_i, []),
+    "cgv_dist_moments_workspace_bytes": (_sz, [_i, _i]),
+    "cgv_dist_moments": (_i, [_p] * 4 + [_i] * 3 + [_p] * 4 + [_p, _sz, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

@@ -1,5 +1,5 @@
 // What the pair kernels that stream a packed copy [S, P] float4 of every structure share (K20 contact_map.hip, K25
-// hbond.hip, K28 lddt.hip, K29 pair_hist.hip): the rule that cuts the structure axis into slices, the walk over the tiles above the
+// hbond.hip, K28 lddt.hip, K29 pair_hist.hip, K30 dist_moments.hip): the rule that cuts the structure axis into slices, the walk over the tiles above the
 // diagonal, and the per-structure counters of the chunk of structures a block stages at a time.  Only integers here, but EVERY FILE THAT INCLUDES THIS IS COMPILED WITH -ffp-contract=off
 // (build.py: SOURCE_FLAGS): the predicates beside it are restated on the host bit for bit.
 #pragma once

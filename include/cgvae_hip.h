@@ -1632,6 +1632,57 @@ int cgv_pairdist_counts(const float* xyz, const int32_t* sel /*[m]*/, const int3
                         int64_t* hist /*[P,n_bins]*/, int64_t* beyond /*[P]*/, int32_t* bad /*[S]*/, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K30  distance-matrix moments of an ensemble -- over the structures of a call, for every pair of selected atoms the sum and
+ * the sum of squares of its distance minus a centre (the mean-distance map, the standard-deviation map, ens_dRMS), and per
+ * structure the sum of the squared deviations of its distances from the centre table (the superposition-free distance RMSD
+ * to a target map).  Nothing in the reference computes it.  Lengths in Angstrom.
+ *   xyz [n_structures,n_atoms,3] fp32         the structures
+ *   sel [m] int32                             the selected atoms.  An index outside [0, n_atoms) reads atom 0 (the host
+ *                                             wrapper refuses such tables); nothing is read out of bounds.
+ *   excluded [m,W] uint32, W = ceil(m / 32)   or NULL (no pair is left out).  Bit (j & 31) of word j >> 5 of row i: the pair
+ *                                             (i, j) enters no sum.  Only the bits j > i are read; the diagonal never
+ *                                             counts; bits past m are ignored.
+ *   center [m,m] fp32                         or NULL (zeros).  Symmetric; only the entries j > i of the pairs that count
+ *                                             are read.  An entry outside [0, 1024] or a NaN is read as 0 (the host wrapper
+ *                                             refuses such tables).
+ * For a good structure s and a pair i < j that is not excluded, in fp32 with every operation individually rounded (no fma;
+ * sqrtf correctly rounded):
+ *   q = sq_dist2(x_i, x_j)   d = sqrtf(q)   e = d - center[i][j]   f = e * e            (csrc/sq_dist.h)
+ *   sum_e[i][j] += rint(e * 2^20)     sum_e2[i][j] += rint(f * 2^20)     dev2[s] += rint(f * 2^12)
+ * The products by a power of two are exact and rint is ties-to-even: a host that restates the arithmetic gets every integer
+ * below exactly; no floating-point result leaves the device.
+ *   sum_e, sum_e2 [m,m] int64                 ADDED to, at [i][j] and [j][i]: a caller cuts a long ensemble into launches and
+ *                                             zeroes them once; the diagonal and the excluded pairs are never written
+ *   dev2 [n_structures] int64                 ADDED to: the caller zeroes it; a bad structure's stays as it was
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate in a selected atom
+ *                                             or a selected atom more than 512 A from the centroid of the selection (fp64);
+ *                                             it enters no sum.  Atoms outside the selection are not looked at.
+ * Launches: one wave per structure gathers the selection into a packed float4 copy in the workspace and decides bad; then
+ *   grid (column tiles of cgv_dist_moments_col_tile(), row tiles of cgv_dist_moments_row_tile(), slices of the structure
+ *   axis) x 256 threads over the tiles that hold a pair i < j: a lane owns a row and 16 columns with their centres and int64
+ *   sums in registers; cgv_dist_moments_chunk() structures at a time go through LDS; dev2 goes through int64 LDS counters of
+ *   the chunk.  Integer sums meet in atomicAdd: the same bits on every call, however the structures are cut.
+ * Overflow: |e| <= 2^10 and f <= 2^20 (the 512 A rule and the centre's range), so with at most cgv_dist_moments_max_total()
+ *   = 2^22 good structures accumulated into one pair of tables |sum_e| <= 2^52 and sum_e2 <= 2^62 (each times 1 + 2^-20 for
+ *   the rounding of d), and dev2 < 2^25 pairs x 2^32.  The CALLER keeps the total; the host wrapper refuses more.
+ * workspace: cgv_dist_moments_workspace_bytes(n_structures, m) bytes (0 beyond a limit), 16-byte aligned, contents need not
+ *   survive.
+ * Limits: 2 <= m <= cgv_dist_moments_max_atoms(), n_structures <= cgv_dist_moments_max_structures() per launch.  Beyond a
+ *   limit the call fails (CGV_E_BADARG) with its reason before any launch and writes nothing; n_structures = 0 returns 0
+ *   and does nothing.  See DESIGN.md (DM row). */
+int cgv_dist_moments_max_atoms(void);
+int cgv_dist_moments_max_structures(void);
+int cgv_dist_moments_max_total(void);
+int cgv_dist_moments_row_tile(void);
+int cgv_dist_moments_col_tile(void);
+int cgv_dist_moments_chunk(void);
+size_t cgv_dist_moments_workspace_bytes(int n_structures, int m);
+int cgv_dist_moments(const float* xyz, const int32_t* sel /*[m]*/, const uint32_t* excluded /*[m,W] or NULL*/,
+                     const float* center /*[m,m] or NULL*/, int n_structures, int n_atoms, int m, int64_t* sum_e /*[m,m]*/,
+                     int64_t* sum_e2 /*[m,m]*/, int64_t* dev2 /*[S]*/, int32_t* bad /*[S]*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
