@@ -69,25 +69,6 @@ def excluded_pairs(bonds, n_atoms: int, sel, depth: int = 3) -> np.ndarray:
     return out
 
 
-def _pack_bits(mask: np.ndarray) -> np.ndarray:
-    """``[r, c]`` bool as the kernel's ``[r, ceil(c/32)]`` uint32: bit ``j & 31`` of word ``j >> 5``."""
-    r, c = mask.shape
-    words = max((c + 31) // 32, 1)
-    padded = np.zeros((r, 32 * words), dtype=bool)
-    padded[:, :c] = mask
-    weights = (np.uint64(1) << np.arange(32, dtype=np.uint64))
-    return np.ascontiguousarray((padded.reshape(r, words, 32).astype(np.uint64) * weights).sum(-1).astype(np.uint32))
-
-
-def _square(mask, size: int, what: str) -> np.ndarray:
-    a = np.asarray(mask)
-    if a.dtype != np.bool_ or a.shape != (size, size):
-        raise ValueError(f"{what} must be a bool array [{size}, {size}], got {a.dtype} {a.shape}")
-    if not np.array_equal(a, a.T):
-        raise ValueError(f"{what} must be symmetric")
-    return a
-
-
 # ----------------------------------------------------------------------------- the launches
 def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=None, groups=None,
                    structures_per_launch: int = 4096, device="cuda") -> dict:
@@ -116,7 +97,7 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
     m = int(table.shape[0])
     if m > lim["atoms"]:
         raise ValueError(f"the selection lists {m} atoms (the kernel holds {lim['atoms']})")
-    excl = np.eye(m, dtype=bool) if excluded is None else (_square(excluded, m, "excluded") | np.eye(m, dtype=bool))
+    excl = np.eye(m, dtype=bool) if excluded is None else (ensemble.square_mask(excluded, m, "excluded") | np.eye(m, dtype=bool))
     order, gstart, ids = None, None, None
     if groups is not None:
         g = np.asarray(groups, dtype=np.int64).reshape(-1)
@@ -129,7 +110,7 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
         table, excl = np.ascontiguousarray(table[order]), excl[np.ix_(order, order)]
         gstart = np.concatenate([[0], np.cumsum(np.bincount(dense, minlength=ids.shape[0]))]).astype(np.int32)
     P = m if groups is None else int(ids.shape[0])
-    nat = None if native is None else _square(native, P, "native")
+    nat = None if native is None else ensemble.square_mask(native, P, "native")
     dev = device_of(x, device)
     M = ensemble.structures_per_launch(structures_per_launch, lim["structures"], 16 * m)
     total = torch.zeros(P, P, dtype=torch.int64, device=dev)
@@ -139,8 +120,8 @@ def contact_counts(xyz, sel=None, cutoff: float = 4.5, excluded=None, native=Non
     if S:
         lib = _lib.load()
         d_sel = torch.from_numpy(table).to(dev)
-        d_excl = torch.from_numpy(_pack_bits(excl).view(np.int32)).to(dev)
-        d_nat = None if nat is None else torch.from_numpy(_pack_bits(nat).view(np.int32)).to(dev)
+        d_excl = torch.from_numpy(ensemble.pack_mask(excl).view(np.int32)).to(dev)
+        d_nat = None if nat is None else torch.from_numpy(ensemble.pack_mask(nat).view(np.int32)).to(dev)
         d_gs = None if gstart is None else torch.from_numpy(gstart).to(dev)
         need = int(lib.cgv_contact_workspace_bytes(min(M, S), m))
         ws = torch.empty((need + 15) // 16 * 4, dtype=torch.float32, device=dev)

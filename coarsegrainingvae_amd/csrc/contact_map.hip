@@ -7,19 +7,20 @@
 // every operation individually rounded, strict <; this file is compiled with -ffp-contract=off): the host restates the
 // test bit for bit, so every integer this file produces is exact.
 //
-// contact_prep_k    one wave per structure, 4 per block.  Pass 1: gathers the m selected atoms through sel into the packed
-//                   copy P [S, m] float4 of the workspace (what the pair kernels stream; w = 0), tests them for finiteness
-//                   and sums them in fp64 -- lane l takes atoms l, l + 64, ... in ascending order, the 64 lane sums meet
-//                   in sq_wave_sum's fixed tree.  Pass 2: the squared distances from the centroid, summed the same way:
-//                   rg2.  A bad structure (a non-finite selected coordinate) gets rg2 = NaN, n_contacts = n_native = -1
-//                   and a packed row of NaN, which is in contact with nothing: the pair kernels need not know of it.
+// The gather, the tile walk, the staging and the chunk's counters are packed_dev.h's.
+// contact_prep_k    one wave per structure, 4 per block.  Pass 1: gather_structure packs the m selected atoms into the
+//                   copy P [S, m] float4 of the workspace (what the pair kernels stream), tests them and gives their fp64
+//                   centroid.  Pass 2: the squared distances from the centroid, lane l taking atoms l, l + 64, ... in
+//                   ascending order, the lane sums meeting in sq_wave_sum's fixed tree: rg2.  A bad structure (a
+//                   non-finite selected coordinate) gets rg2 = NaN, n_contacts = n_native = -1 and a packed row of NaN,
+//                   which is in contact with nothing: the pair kernels need not know of it.
 // contact_pairs_k   256 threads, grid (column tiles of 128, row tiles of 64, slices of the structure axis); tiles without
 //                   a pair i < j return.  Thread t owns row t & 63 and the 32 columns of wave t >> 6 -- one word of the
 //                   bit masks -- and keeps their 32 counters in registers.  CT_CHUNK structures at a time go through LDS
-//                   (rows and columns of the tile as float4: the row read is one ds_read_b128 per lane, a column read is
-//                   the same address in every lane); per structure a lane's hits under its mask go to the chunk's
-//                   counters in LDS, which the block adds to n_contacts / n_native once per structure.  At the end a
-//                   nonzero counter is added to counts[i][j] and counts[j][i].
+//                   (the row read is one ds_read_b128 per lane, a column read is the same address in every lane); per
+//                   structure a lane's hits under its mask go to the chunk's counters, which the block adds to
+//                   n_contacts / n_native once per structure.  At the end a nonzero counter is added to counts[i][j] and
+//                   counts[j][i].
 // contact_groups_k  one wave per pair of groups A < B, grid (G, G, slices).  The lanes tile the |A| x |B| atom pairs (the
 //                   width of B rounded up to a power of two, at most 64); for 64 structures at a time a lane tests its
 //                   pairs (the exclusion bit of a pair is read once per 64 structures) and keeps one bit per structure;
@@ -46,26 +47,16 @@ __global__ __launch_bounds__(256) void contact_prep_k(const float* __restrict__ 
                                                       int* __restrict__ n_native) {
   const int lane = threadIdx.x & 63, s = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (s >= S) return;                                        // whole waves leave
-  const float* base = xyz + (size_t)s * n * 3;
   float4* row = packed + (size_t)s * m;
-  double sx = 0.0, sy = 0.0, sz = 0.0;
-  bool ok = true;
-  for (int k = lane; k < m; k += 64) {
-    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
-    ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    row[k] = make_float4(p.x, p.y, p.z, 0.f);
-    sx += (double)p.x, sy += (double)p.y, sz += (double)p.z;
-  }
-  const bool is_bad = __any(!ok) != 0;
-  const double cx = __shfl(sq_wave_sum(sx), 0) / (double)m, cy = __shfl(sq_wave_sum(sy), 0) / (double)m,
-               cz = __shfl(sq_wave_sum(sz), 0) / (double)m;
+  double c[3];
+  const bool is_bad = !gather_structure(xyz + (size_t)s * n * 3, [=](int k) { return sel[k]; }, n, m, row, lane, c);
   double g = 0.0;
   for (int k = lane; k < m; k += 64) {
     const float4 p = row[k];                                 // this lane wrote it
-    const double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;
+    const double dx = (double)p.x - c[0], dy = (double)p.y - c[1], dz = (double)p.z - c[2];
     g += (dx * dx + dy * dy) + dz * dz;
-    if (is_bad) row[k] = make_float4(NAN, NAN, NAN, 0.f);
   }
+  if (is_bad) poison_row(row, m, lane);
   g = sq_wave_sum(g);
   if (lane == 0) {
     if (rg2 != nullptr) rg2[s] = is_bad ? (double)NAN : g / (double)m;
@@ -81,17 +72,15 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
                                                        float cutoff2, int* __restrict__ counts, int* __restrict__ n_contacts,
                                                        int* __restrict__ n_native) {
   __shared__ float4 st[CT_CHUNK][CT_ROWS + CT_COLS];
-  __shared__ ChunkHits<CT_CHUNK> hits;
+  __shared__ ChunkCounts<int, CT_CHUNK, 2> hits;             // per structure: contacts, native contacts
   const int r0 = (int)blockIdx.y * CT_ROWS, c0 = (int)blockIdx.x * CT_COLS;
   if (!upper_tile_live(r0, c0, CT_COLS)) return;             // no column of the tile is above a row of it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = r0 + lane, cb = c0 + 32 * wave;            // this thread's row and the first of its 32 columns
   // bit u: the pair (row, cb + u) is this thread's to count -- inside the selection, above the diagonal, not excluded
-  uint32_t ok = 0, nat = 0;
-  if (row < m && cb < m) {
-    ok = upper_pair_word(row, cb, m) & ~excl[(size_t)row * words + (cb >> 5)];
-    if (native != nullptr) nat = ok & native[(size_t)row * words + (cb >> 5)];
-  }
+  const uint32_t ok = upper_pair_bits<32>(row, cb, m, excl, words);
+  uint32_t nat = 0;
+  if (ok != 0 && native != nullptr) nat = ok & native[(size_t)row * words + (cb >> 5)];
   const bool wave_live = __any(ok != 0) != 0;
   int cnt[32];
 #pragma unroll
@@ -99,13 +88,8 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
   const int s_begin = (int)blockIdx.z * per, s_end = min(S, s_begin + per);
   for (int s0 = s_begin; s0 < s_end; s0 += CT_CHUNK) {
     __syncthreads();                                         // the previous chunk has been read and its hits flushed
-    for (int e = tid; e < CT_CHUNK * (CT_ROWS + CT_COLS); e += 256) {
-      const int sl = e / (CT_ROWS + CT_COLS), a = e - sl * (CT_ROWS + CT_COLS);
-      const int at = a < CT_ROWS ? r0 + a : c0 + a - CT_ROWS;
-      float4 v = make_float4(NAN, NAN, NAN, 0.f);            // past the slice or the selection: in contact with nothing
-      if (s0 + sl < s_end && at < m) v = packed[(size_t)(s0 + sl) * m + at];
-      st[sl][a] = v;
-    }
+    // NaN past the slice or the selection: in contact with nothing
+    stage_chunk<CT_CHUNK, CT_ROWS, CT_COLS>(st, packed, m, r0, c0, s0, s_end, tid, NAN);
     hits.zero(tid);
     __syncthreads();
     if (wave_live) {
@@ -122,8 +106,8 @@ __global__ __launch_bounds__(256) void contact_pairs_k(const float4* __restrict_
         }
         hit &= ok;
         if (hit != 0) {
-          hits.add(0, sl, __popc(hit));
-          if ((hit & nat) != 0) hits.add(1, sl, __popc(hit & nat));
+          hits.add(sl, 0, __popc(hit));
+          if ((hit & nat) != 0) hits.add(sl, 1, __popc(hit & nat));
         }
       }
     }
@@ -200,8 +184,7 @@ static int ct_check(const void* xyz, const void* sel, const void* excl, int S, i
   else if (!(cutoff2 >= 0.f)) *why = "cutoff2 must be a number >= 0";
   else if (S == 0) return 1;
   else if (!xyz || !sel || !excl || !n_contacts || !n_native || !bad) *why = "null pointer";
-  else if (!workspace || workspace_bytes < (size_t)S * (size_t)m * sizeof(float4)) *why = "workspace smaller than cgv_contact_workspace_bytes()";
-  else if (((uintptr_t)workspace & 15) != 0) *why = "workspace must be 16-byte aligned";
+  else *why = workspace_why(workspace, workspace_bytes, (size_t)S * (size_t)m * sizeof(float4), "workspace smaller than cgv_contact_workspace_bytes()");
   return 0;
 }
 
@@ -232,10 +215,9 @@ int cgv_contact_counts(const float* xyz, const int32_t* sel, const uint32_t* exc
                      m, packed, rg2, bad, n_contacts, n_native);
   int rc = cgv::check_launch("cgv_contact_counts (preparation)");
   if (rc || m < 2) return rc;
-  const int nr = (m + cgv::CT_ROWS - 1) / cgv::CT_ROWS, nc = (m + cgv::CT_COLS - 1) / cgv::CT_COLS;
   int per;
-  const int slices = cgv::struct_slices(n_structures, cgv::upper_live_tiles(nr, nc, cgv::CT_ROWS, cgv::CT_COLS), cgv::CT_CHUNK, &per);
-  hipLaunchKernelGGL(cgv::contact_pairs_k, dim3((unsigned)nc, (unsigned)nr, (unsigned)slices), dim3(256), 0, st, packed, excluded,
+  const dim3 grid = cgv::pair_grid(n_structures, m, cgv::CT_ROWS, cgv::CT_COLS, cgv::CT_CHUNK, false, &per);
+  hipLaunchKernelGGL(cgv::contact_pairs_k, grid, dim3(256), 0, st, packed, excluded,
                      native, n_structures, m, (m + 31) / 32, per, cutoff2, counts, n_contacts, n_native);
   return cgv::check_launch("cgv_contact_counts");
 }

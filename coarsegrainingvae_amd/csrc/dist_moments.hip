@@ -28,16 +28,17 @@
 //   a term of dev2      rint(f * 2^12) <= 2^32 (1 + 2^-20); fewer than 2^25 pairs of 2^13 atoms: dev2[s] < 2^58
 // A thread's registers hold one pair over the structures of ONE launch (<= 2^20): |.| <= 2^60.
 //
-// dist_prep_k     one wave per structure, 4 per block: gathers the m selected atoms through sel into the packed copy
-//                 [S, m] float4 of the workspace (what the pair kernel streams; w = 0), sums them in fp64 and decides bad.
+// The gather with its centroid, the tile walk, the thread's mask bits, the staging and the chunk's counters are packed_dev.h's.
+// dist_prep_k     one wave per structure, 4 per block: gather_structure fills the packed copy [S, m] float4 of the workspace
+//                 (what the pair kernel streams) and gives the fp64 centroid; the 512 A test decides bad.
 // dist_pairs_k    256 threads, grid (column tiles of 64, row tiles of 64, slices of the structure axis); tiles without a pair
-//                 i < j return (packed_dev.h: upper_tile_live).  Thread t owns row t & 63 and the 16 columns of wave t >> 6
-//                 -- half a word of the mask -- and keeps in registers their 16 centres and 2 x 16 int64 sums (64 VGPRs;
-//                 K20's 32 columns per thread would be 128 for the sums alone).  DM_CHUNK structures at a time go through
-//                 LDS (row atom: one ds_read_b128 per lane, column atom: one address for the wave); bad structures are
-//                 skipped, so nothing relies on NaN.  A lane's sum of rint(f * 2^12) over its counted pairs of a structure
-//                 goes to the chunk's int64 counters in LDS, which the block adds to dev2 once per structure.  At the end a
-//                 nonzero sum is added to [i][j] and [j][i] of the caller's tables, one 64-bit atomicAdd each.
+//                 i < j return.  Thread t owns row t & 63 and the 16 columns of wave t >> 6 -- half a word of the mask --
+//                 and keeps in registers their 16 centres and 2 x 16 int64 sums (64 VGPRs; K20's 32 columns per thread
+//                 would be 128 for the sums alone).  DM_CHUNK structures at a time go through LDS (row atom: one
+//                 ds_read_b128 per lane, column atom: one address for the wave); bad structures are skipped, so nothing
+//                 relies on NaN.  A lane's sum of rint(f * 2^12) over its counted pairs of a structure goes to the chunk's
+//                 int64 counter, which the block adds to dev2 once per structure.  At the end a nonzero sum is added to
+//                 [i][j] and [j][i] of the caller's tables, one 64-bit atomicAdd each.
 // Sums of integers meet in atomicAdd (LDS and global), whose order does not matter: two runs give the same bits, and
 // nothing depends on how the caller cuts the structures into launches or struct_slices cuts a launch into slices.
 #include <math.h>
@@ -59,47 +60,23 @@ constexpr double DM_MAX_RADIUS = 512.0;      // from the centroid of the selecti
 constexpr float DM_MAX_CENTER = 1024.f;      // the largest centre taken as it is
 constexpr float DM_SCALE = 1048576.f;        // 2^20: sum_e and sum_e2
 constexpr float DM_SCALE_DEV = 4096.f;       // 2^12: dev2
-static_assert(DM_COLS == 4 * DM_PER && 32 % DM_PER == 0, "a thread's columns lie in one word of the mask");
-
-// the chunk's per-structure sums in LDS (packed_dev.h: ChunkCounts with one int64 member per structure)
-template <int CHUNK>
-struct ChunkSums {
-  unsigned long long v[CHUNK];
-  __device__ __forceinline__ void zero(int tid) { if (tid < CHUNK) v[tid] = 0ull; }
-  __device__ __forceinline__ void add(int sl, unsigned long long x) { atomicAdd(&v[sl], x); }
-  __device__ __forceinline__ void flush(int s0, int s_end, int tid, unsigned long long* __restrict__ table) {
-    if (tid < CHUNK) {
-      const unsigned long long x = v[tid];
-      if (x != 0ull && s0 + tid < s_end) atomicAdd(table + s0 + tid, x);
-    }
-  }
-};
+static_assert(DM_COLS == 4 * DM_PER, "four waves share a tile's columns");
 
 // grid: 4 structures per block
 __global__ __launch_bounds__(256) void dist_prep_k(const float* __restrict__ xyz, const int* __restrict__ sel, int S, int n, int m,
                                                    float4* __restrict__ packed, int* __restrict__ bad) {
   const int lane = threadIdx.x & 63, s = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (s >= S) return;                                        // whole waves leave
-  const float* base = xyz + (size_t)s * n * 3;
   float4* row = packed + (size_t)s * m;
-  double sx = 0.0, sy = 0.0, sz = 0.0;
-  bool ok = true;
-  for (int k = lane; k < m; k += 64) {
-    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
-    ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    row[k] = make_float4(p.x, p.y, p.z, 0.f);
-    sx += (double)p.x, sy += (double)p.y, sz += (double)p.z;
-  }
-  const double cx = __shfl(sq_wave_sum(sx), 0) / (double)m, cy = __shfl(sq_wave_sum(sy), 0) / (double)m,
-               cz = __shfl(sq_wave_sum(sz), 0) / (double)m;
+  double c[3];
+  bool ok = gather_structure(xyz + (size_t)s * n * 3, [=](int k) { return sel[k]; }, n, m, row, lane, c);
   for (int k = lane; k < m; k += 64) {
     const float4 p = row[k];                                 // this lane wrote it
-    const double dx = (double)p.x - cx, dy = (double)p.y - cy, dz = (double)p.z - cz;
+    const double dx = (double)p.x - c[0], dy = (double)p.y - c[1], dz = (double)p.z - c[2];
     ok = ok && ((dx * dx + dy * dy) + dz * dz <= DM_MAX_RADIUS * DM_MAX_RADIUS);     // false for a NaN
   }
   const bool is_bad = __any(!ok) != 0;
-  if (is_bad)
-    for (int k = lane; k < m; k += 64) row[k] = make_float4(NAN, NAN, NAN, 0.f);
+  if (is_bad) poison_row(row, m, lane);
   if (lane == 0) bad[s] = is_bad ? 1 : 0;
 }
 
@@ -110,18 +87,13 @@ __global__ __launch_bounds__(256) void dist_pairs_k(const float4* __restrict__ p
                                                     unsigned long long* __restrict__ sum_e2, unsigned long long* __restrict__ dev2) {
   __shared__ float4 st[DM_CHUNK][DM_STAGE];
   __shared__ int skip[DM_CHUNK];                             // 1: bad, or past the slice
-  __shared__ ChunkSums<DM_CHUNK> dsum;
+  __shared__ ChunkCounts<unsigned long long, DM_CHUNK, 1> dsum;   // per structure: its sum of rint(f * 2^12)
   const int r0 = (int)blockIdx.y * DM_ROWS, c0 = (int)blockIdx.x * DM_COLS;
   if (!upper_tile_live(r0, c0, DM_COLS)) return;             // no column of the tile is above a row of it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int row = r0 + lane, cb = c0 + DM_PER * wave;        // this thread's row and the first of its 16 columns
   // bit u: the pair (row, cb + u) is this thread's to sum -- inside the selection, above the diagonal, not excluded
-  uint32_t ok = 0;
-  if (row < m && cb < m) {
-    uint32_t w = upper_pair_word(row, cb & ~31, m);
-    if (excl != nullptr) w &= ~excl[(size_t)row * words + (cb >> 5)];
-    ok = (w >> (cb & 31)) & ((1u << DM_PER) - 1u);
-  }
+  const uint32_t ok = upper_pair_bits<DM_PER>(row, cb, m, excl, words);
   const bool wave_live = __any(ok != 0) != 0;
   float ctr[DM_PER];
   long long a1[DM_PER], a2[DM_PER];                          // sums of rint(e * 2^20) and of rint(f * 2^20) over the slice
@@ -135,14 +107,8 @@ __global__ __launch_bounds__(256) void dist_pairs_k(const float4* __restrict__ p
   const int s_begin = (int)blockIdx.z * per, s_end = min(S, s_begin + per);
   for (int s0 = s_begin; s0 < s_end; s0 += DM_CHUNK) {
     __syncthreads();                                         // the previous chunk has been read and its sums flushed
-    if (tid < DM_CHUNK) skip[tid] = s0 + tid < s_end && bad[s0 + tid] == 0 ? 0 : 1;
-    for (int e = tid; e < DM_CHUNK * DM_STAGE; e += 256) {
-      const int sl = e / DM_STAGE, a = e - sl * DM_STAGE;
-      const int at = a < DM_ROWS ? r0 + a : c0 + a - DM_ROWS;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);            // past the slice or the selection: outside every mask
-      if (s0 + sl < s_end && at < m) v = packed[(size_t)(s0 + sl) * m + at];
-      st[sl][a] = v;
-    }
+    // 0 past the slice or the selection: outside every mask
+    stage_chunk<DM_CHUNK, DM_ROWS, DM_COLS>(st, packed, m, r0, c0, s0, s_end, tid, 0.f, bad, skip);
     dsum.zero(tid);
     __syncthreads();
     if (wave_live) {
@@ -162,7 +128,7 @@ __global__ __launch_bounds__(256) void dist_pairs_k(const float4* __restrict__ p
           const unsigned long long g = (unsigned long long)rintf(__fmul_rn(f, DM_SCALE_DEV));
           dev += ((ok >> u) & 1u) != 0 ? g : 0ull;
         }
-        if (dev != 0ull) dsum.add(sl, dev);
+        if (dev != 0ull) dsum.add(sl, 0, dev);
       }
     }
     __syncthreads();
@@ -205,17 +171,16 @@ int cgv_dist_moments(const float* xyz, const int32_t* sel, const uint32_t* exclu
   CGV_REQUIRE(m <= cgv::DM_MAX_ATOMS, "m <= cgv_dist_moments_max_atoms()");
   if (S == 0) return 0;
   CGV_REQUIRE(xyz && sel && sum_e && sum_e2 && dev2 && bad, "null pointer");
-  CGV_REQUIRE(workspace && workspace_bytes >= cgv::dm_workspace(S, m), "workspace smaller than cgv_dist_moments_workspace_bytes()");
-  CGV_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  const char* why = cgv::workspace_why(workspace, workspace_bytes, cgv::dm_workspace(S, m), "workspace smaller than cgv_dist_moments_workspace_bytes()");
+  CGV_REQUIRE(why == nullptr, why);
   hipStream_t st = (hipStream_t)stream;
   float4* packed = (float4*)workspace;
   hipLaunchKernelGGL(cgv::dist_prep_k, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, xyz, sel, S, n_atoms, m, packed, bad);
   int rc = cgv::check_launch("cgv_dist_moments (preparation)");
   if (rc) return rc;
-  const int nr = (m + cgv::DM_ROWS - 1) / cgv::DM_ROWS, nc = (m + cgv::DM_COLS - 1) / cgv::DM_COLS;
   int per;
-  const int slices = cgv::struct_slices(S, cgv::upper_live_tiles(nr, nc, cgv::DM_ROWS, cgv::DM_COLS), cgv::DM_CHUNK, &per);
-  hipLaunchKernelGGL(cgv::dist_pairs_k, dim3((unsigned)nc, (unsigned)nr, (unsigned)slices), dim3(256), 0, st, (const float4*)packed,
+  const dim3 grid = cgv::pair_grid(S, m, cgv::DM_ROWS, cgv::DM_COLS, cgv::DM_CHUNK, false, &per);
+  hipLaunchKernelGGL(cgv::dist_pairs_k, grid, dim3(256), 0, st, (const float4*)packed,
                      excluded, center, (const int*)bad, S, m, (m + 31) / 32, per, (unsigned long long*)sum_e,
                      (unsigned long long*)sum_e2, (unsigned long long*)dev2);
   return cgv::check_launch("cgv_dist_moments");

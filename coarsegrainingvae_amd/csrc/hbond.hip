@@ -15,16 +15,17 @@
 // tests are cos(D-H-A) < cos(angle) without a square root or a division.  The host restates the test bit for bit, so every
 // integer this file produces is exact.  A structure with a non-finite coordinate among its D, H or A atoms is bad.
 //
-// hbond_prep_k    one wave per structure, 4 per block: gathers the table atoms through don_h, don_d and acc into the packed
-//                 copy [S, 2 nH + nA] float4 of the workspace (H rows, then D rows, then acceptors; w = 0), what the pair
-//                 kernel streams, and tests them for finiteness.  A bad structure gets n_hbonds = n_native = -1 and a
-//                 packed row of NaN, which bonds with nothing: the pair kernel need not know of it.
+// hbond_prep_k    one wave per structure, 4 per block: packed_dev.h's gather_structure with the index (don_h | don_d | acc)
+//                 fills the packed copy [S, 2 nH + nA] float4 of the workspace (H rows, then D rows, then acceptors), what
+//                 the pair kernel streams.  A bad structure gets n_hbonds = n_native = -1 and a packed row of NaN, which
+//                 bonds with nothing: the pair kernel need not know of it.
 // hbond_pairs_k   256 threads, grid (words of 64 acceptors, row tiles of 32 hydrogens, slices of the structure axis).  A
 //                 lane owns an acceptor column, wave w the rows 8 w .. 8 w + 7 of the tile, whose 8 counters a lane keeps in
-//                 registers.  HB_CHUNK structures at a time go through LDS as float4: a lane's acceptor is one
-//                 ds_read_b128, H and D of a row are the same address in every lane.  The wave's ballot of the predicate,
-//                 ANDed with the row's word of pairs that count, IS the word of `bits`; its popcount goes to the chunk's
-//                 counters in LDS, which the block adds to n_hbonds / n_native once per structure.  At the end a nonzero
+//                 registers.  HB_CHUNK structures at a time go through LDS as float4 (staged here, not by stage_chunk: a
+//                 tile has three ranges of the packed row, not two): a lane's acceptor is one ds_read_b128, H and D of a
+//                 row are the same address in every lane.  The wave's ballot of the predicate, ANDed with the row's word
+//                 of pairs that count, IS the word of `bits`; its popcount goes to the chunk's counters (packed_dev.h:
+//                 ChunkCounts), which the block adds to n_hbonds / n_native once per structure.  At the end a nonzero
 //                 counter is added to pair_counts.
 // Sums of integers meet in atomicAdd, whose order does not matter, and every word of `bits` has one writer: two runs give the
 // same bits, and nothing depends on how the caller cuts the structures into launches.
@@ -52,18 +53,10 @@ __global__ __launch_bounds__(256) void hbond_prep_k(const float* __restrict__ xy
   const int lane = threadIdx.x & 63, s = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (s >= S) return;                                        // whole waves leave
   const int P = 2 * nH + nA;
-  const float* base = xyz + (size_t)s * n * 3;
   float4* row = packed + (size_t)s * P;
-  bool ok = true;
-  for (int k = lane; k < P; k += 64) {
-    const int at = sel_atom(k < nH ? don_h[k] : k < 2 * nH ? don_d[k - nH] : acc[k - 2 * nH], n);
-    const f3 p = ld3(base + 3 * (size_t)at);
-    ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    row[k] = make_float4(p.x, p.y, p.z, 0.f);
-  }
-  const bool is_bad = __any(!ok) != 0;
-  if (is_bad)
-    for (int k = lane; k < P; k += 64) row[k] = make_float4(NAN, NAN, NAN, 0.f);   // this lane wrote it
+  const auto at = [=](int k) { return k < nH ? don_h[k] : k < 2 * nH ? don_d[k - nH] : acc[k - 2 * nH]; };
+  const bool is_bad = !gather_structure(xyz + (size_t)s * n * 3, at, n, P, row, lane);
+  if (is_bad) poison_row(row, P, lane);
   if (lane == 0) {
     bad[s] = is_bad ? 1 : 0;
     n_hbonds[s] = is_bad ? -1 : 0;
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(256) void hbond_pairs_k(const float4* __restrict__ 
                                                      unsigned long long* __restrict__ pair_counts, int* __restrict__ n_hbonds,
                                                      int* __restrict__ n_native, unsigned long long* __restrict__ bits) {
   __shared__ float4 st[HB_CHUNK][HB_STAGE];
-  __shared__ ChunkHits<HB_CHUNK> hits;
+  __shared__ ChunkCounts<int, HB_CHUNK, 2> hits;             // per structure: bonds, native bonds
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int word = (int)blockIdx.x, r0 = (int)blockIdx.y * HB_ROWS, c0 = word * HB_COLS;
   const int P = 2 * nH + nA, rw = r0 + HB_RPW * wave;        // the first of this wave's rows
@@ -131,8 +124,8 @@ __global__ __launch_bounds__(256) void hbond_pairs_k(const float4* __restrict__ 
         if (bits != nullptr && lane == 0 && rw + u < nH) bits[((size_t)(s0 + sl) * nH + (rw + u)) * words + word] = w;
       }
       if (lane == 0) {
-        if (nh != 0) hits.add(0, sl, nh);
-        if (nn != 0) hits.add(1, sl, nn);
+        if (nh != 0) hits.add(sl, 0, nh);
+        if (nn != 0) hits.add(sl, 1, nn);
       }
     }
     __syncthreads();
@@ -178,8 +171,8 @@ int cgv_hbond_counts(const float* xyz, const int32_t* don_h, const int32_t* don_
   CGV_REQUIRE(c2 >= 0.f && c2 <= 1.f, "c2 must be the squared cosine of an angle in [90, 180) degrees");
   if (S == 0) return 0;
   CGV_REQUIRE(xyz && don_h && don_d && acc && excluded && pair_counts && n_hbonds && n_native && bad, "null pointer");
-  CGV_REQUIRE(workspace && workspace_bytes >= cgv::hb_workspace(S, nH, nA), "workspace smaller than cgv_hbond_workspace_bytes()");
-  CGV_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  const char* why = cgv::workspace_why(workspace, workspace_bytes, cgv::hb_workspace(S, nH, nA), "workspace smaller than cgv_hbond_workspace_bytes()");
+  CGV_REQUIRE(why == nullptr, why);
   hipStream_t st = (hipStream_t)stream;
   float4* packed = (float4*)workspace;
   hipLaunchKernelGGL(cgv::hbond_prep_k, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, xyz, don_h, don_d, acc, S, n_atoms, nH, nA,

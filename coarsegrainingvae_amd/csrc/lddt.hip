@@ -15,20 +15,21 @@
 // produces is exact; no floating-point number leaves the device.  A model structure with a non-finite selected coordinate,
 // or scored against a reference with one, is bad: its six counts are -1 and it enters no sum.
 //
-// lddt_prep_k    one wave per structure, 4 per block; launched for the references, then for the models.  Gathers the m
-//                selected atoms through sel into a packed copy [count, m] float4 of the workspace (what the pair kernel
-//                streams; w = 0) and tests them for finiteness.  The reference launch writes a flag per reference, the model
-//                launch reads the flag of its structure's reference and writes bad and the six struct_counts (0 or -1).
+// lddt_prep_k    one wave per structure, 4 per block; launched for the references, then for the models.  packed_dev.h's
+//                gather_structure fills a packed copy [count, m] float4 of the workspace (what the pair kernel streams).
+//                The reference launch writes a flag per reference, the model launch reads the flag of its structure's
+//                reference and writes bad and the six struct_counts (0 or -1).
 // lddt_pairs_k   256 threads, grid (column tiles of 128, row tiles of 64, slices of the structure axis) over the FULL m x m
 //                grid of ordered pairs: thread t owns row t & 63 and the 32 columns of wave t >> 6 -- one word of the bit
 //                masks -- and keeps the row's six counters in registers, so atom_counts needs no transposed add.  LD_CHUNK
 //                structures at a time go through LDS (row atom: one ds_read_b128 per lane, column atom: one address for the
-//                wave).  What depends on the reference alone -- sqrtf(q0) of the thread's 32 pairs and their inclusion word
+//                wave), staged here and not by stage_chunk: one loop fills a model's slot and, where it is needed, its
+//                reference's, and skips a slot by the table the first thread wrote.  What depends on the reference alone -- sqrtf(q0) of the thread's 32 pairs and their inclusion word
 //                -- stays in registers and is recomputed (and the reference staged) only when ref_index changes between
 //                consecutive good structures: a single native reference costs one distance per pair, not two.  The
 //                per-structure counts take the pairs above the diagonal only (tiles wholly below it add nothing): three
-//                packed wave sums, lane 0 adds them to the chunk's counters in LDS, the block to struct_counts once per
-//                structure.  Bad structures are skipped, so nothing relies on NaN.  At the end a nonzero row counter is
+//                packed wave sums, lane 0 adds them to the chunk's counters (packed_dev.h: ChunkCounts), the block to
+//                struct_counts once per structure.  Bad structures are skipped, so nothing relies on NaN.  At the end a nonzero row counter is
 //                added to atom_counts.
 // Sums of integers meet in atomicAdd (LDS and global), whose order does not matter: two runs give the same bits, and nothing
 // depends on how the caller cuts the structures into launches.
@@ -55,15 +56,7 @@ __global__ __launch_bounds__(256) void lddt_prep_k(const float* __restrict__ xyz
                                                    int* __restrict__ bad, int* __restrict__ struct_counts) {
   const int lane = threadIdx.x & 63, s = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (s >= count) return;                                    // whole waves leave
-  const float* base = xyz + (size_t)s * n * 3;
-  float4* row = packed + (size_t)s * m;
-  bool ok = true;
-  for (int k = lane; k < m; k += 64) {
-    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
-    ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    row[k] = make_float4(p.x, p.y, p.z, 0.f);
-  }
-  bool is_bad = __any(!ok) != 0;
+  bool is_bad = !gather_structure(xyz + (size_t)s * n * 3, [=](int k) { return sel[k]; }, n, m, packed + (size_t)s * m, lane);
   if (refbad_out != nullptr) {
     if (lane == 0) refbad_out[s] = is_bad ? 1 : 0;
     return;
@@ -82,7 +75,7 @@ __global__ __launch_bounds__(256) void lddt_pairs_k(const float4* __restrict__ P
                                                     int* __restrict__ struct_counts, unsigned long long* __restrict__ atom_counts) {
   __shared__ float4 sm[LD_CHUNK][LD_STAGE];                  // the models of the chunk
   __shared__ float4 sr[LD_CHUNK][LD_STAGE];                  // the reference of a model, where it differs from the one before
-  __shared__ ChunkCounts<LD_CHUNK, LD_N> hits;
+  __shared__ ChunkCounts<int, LD_CHUNK, LD_N> hits;
   __shared__ int sref[LD_CHUNK];                             // the reference of a structure; -1: skipped (bad, past the slice)
   __shared__ int sneed[LD_CHUNK];                            // 1: its reference is staged
   const int r0 = (int)blockIdx.y * LD_ROWS, c0 = (int)blockIdx.x * LD_COLS;
@@ -92,14 +85,14 @@ __global__ __launch_bounds__(256) void lddt_pairs_k(const float4* __restrict__ P
   // off the diagonal, not excluded.  `above`: cb + u > row, the pairs the per-structure counts take
   uint32_t okl = 0, okc = 0, above = 0;
   if (row < m && cb < m) {
-    const uint32_t inside = m - cb >= 32 ? 0xffffffffu : (1u << (m - cb)) - 1u;
+    const uint32_t inside = word_inside(cb, m);
     const uint32_t off = row >= cb && row < cb + 32 ? ~(1u << (row - cb)) : 0xffffffffu;
     okl = inside & off & ~excl_l[(size_t)row * words + (cb >> 5)];
     okc = inside & off & ~excl_c[(size_t)row * words + (cb >> 5)];
-    above = row < cb ? 0xffffffffu : row >= cb + 31 ? 0u : 0xffffffffu << (row - cb + 1);
+    above = word_above(row, cb);
   }
   const bool wave_live = __any((okl | okc) != 0) != 0;
-  const bool tile_above = c0 + LD_COLS - 1 > r0;             // the same for the whole block
+  const bool tile_above = upper_tile_live(r0, c0, LD_COLS);  // the same for the whole block
   float cc2[32];                                             // c * c of a pair, -1 where c > 0 fails: q < cc2 is the clash test
   {
     const float ri = row < m ? radii[row] : 0.f;
@@ -251,8 +244,8 @@ int cgv_lddt_counts(const float* xyz, const float* ref_xyz, const int32_t* ref_i
   CGV_REQUIRE(T >= 1, "structures need at least one reference");
   CGV_REQUIRE(xyz && ref_xyz && ref_index && sel && excl_lddt && excl_clash && radii && struct_counts && atom_counts && bad, "null pointer");
   for (int s = 0; s < S; ++s) CGV_REQUIRE(ref_index[s] >= 0 && ref_index[s] < T, "ref_index outside [0, n_references)");
-  CGV_REQUIRE(workspace && workspace_bytes >= cgv::ld_workspace(S, T, m), "workspace smaller than cgv_lddt_workspace_bytes()");
-  CGV_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  const char* why = cgv::workspace_why(workspace, workspace_bytes, cgv::ld_workspace(S, T, m), "workspace smaller than cgv_lddt_workspace_bytes()");
+  CGV_REQUIRE(why == nullptr, why);
   hipStream_t st = (hipStream_t)stream;
   float4* P = (float4*)workspace;
   float4* Q = P + (size_t)S * m;
@@ -271,10 +264,9 @@ int cgv_lddt_counts(const float* xyz, const float* ref_xyz, const int32_t* ref_i
                      (const int*)refbad, (int*)nullptr, bad, struct_counts);
   rc = cgv::check_launch("cgv_lddt_counts (preparation)");
   if (rc || m < 2) return rc;
-  const int nr = (m + cgv::LD_ROWS - 1) / cgv::LD_ROWS, nc = (m + cgv::LD_COLS - 1) / cgv::LD_COLS;
   int per;
-  const int slices = cgv::struct_slices(S, nr * nc, cgv::LD_CHUNK, &per);
-  hipLaunchKernelGGL(cgv::lddt_pairs_k, dim3((unsigned)nc, (unsigned)nr, (unsigned)slices), dim3(256), 0, st, (const float4*)P,
+  const dim3 grid = cgv::pair_grid(S, m, cgv::LD_ROWS, cgv::LD_COLS, cgv::LD_CHUNK, true, &per);   // the full grid: ordered pairs
+  hipLaunchKernelGGL(cgv::lddt_pairs_k, grid, dim3(256), 0, st, (const float4*)P,
                      (const float4*)Q, (const int*)ridx, (const int*)bad, excl_lddt, excl_clash, radii, S, m, (m + 31) / 32, per,
                      radius2, t0, t1, t2, t3, tolerance, struct_counts, (unsigned long long*)atom_counts);
   return cgv::check_launch("cgv_lddt_counts");

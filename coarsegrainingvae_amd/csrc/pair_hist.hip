@@ -13,14 +13,14 @@
 // so every integer this file produces is exact; no floating-point number leaves the device.  A structure with a non-finite
 // selected coordinate is bad: bad[s] = 1 and it enters no sum.
 //
-// pairdist_prep_k    one wave per structure, 4 per block: gathers the m selected atoms through sel into the packed copy
-//                    [S, m] float4 of the workspace (what the pair kernel streams; w = 0) and decides bad.
+// The gather, the tile walk, the thread's mask word and the staging are packed_dev.h's.
+// pairdist_prep_k    one wave per structure, 4 per block: gather_structure fills the packed copy [S, m] float4 of the
+//                    workspace (what the pair kernel streams) and decides bad.
 // pairdist_pairs_k   256 threads, grid (column tiles of 128, row tiles of 64, slices of the structure axis); tiles without a
-//                    pair i < j return (packed_dev.h: upper_tile_live).  Thread t owns row t & 63 and the 32 columns of wave
-//                    t >> 6 -- one word of the mask -- and keeps in registers, for each of the 32 pairs, where its class
-//                    pair's row of the histogram starts.  PD_CHUNK structures at a time go through LDS (row atom: one
-//                    ds_read_b128 per lane, column atom: one address for the wave); bad structures are skipped, so nothing
-//                    relies on NaN.  The block's histogram is private in LDS, P rows of n_bins + 1 32-bit counters (the last
+//                    pair i < j return.  Thread t owns row t & 63 and the 32 columns of wave t >> 6 -- one word of the
+//                    mask -- and keeps in registers, for each of the 32 pairs, where its class pair's row of the histogram
+//                    starts.  PD_CHUNK structures at a time go through LDS (row atom: one ds_read_b128 per lane, column
+//                    atom: one address for the wave); bad structures are skipped, so nothing relies on NaN.  The block's histogram is private in LDS, P rows of n_bins + 1 32-bit counters (the last
 //                    one is `beyond`).  An in-range pair is one LDS integer atomic; the pairs at r_max or farther -- most
 //                    pairs of a large molecule, and ONE address per class pair, on which the lanes of a wave would
 //                    serialise -- are counted in 32 registers, as K20 counts its contacts, and reach the LDS counter once
@@ -69,16 +69,8 @@ __global__ __launch_bounds__(256) void pairdist_prep_k(const float* __restrict__
                                                        float4* __restrict__ packed, int* __restrict__ bad) {
   const int lane = threadIdx.x & 63, s = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (s >= S) return;                                        // whole waves leave
-  const float* base = xyz + (size_t)s * n * 3;
-  float4* row = packed + (size_t)s * m;
-  bool ok = true;
-  for (int k = lane; k < m; k += 64) {
-    const f3 p = ld3(base + 3 * (size_t)sel_atom(sel[k], n));
-    ok = ok && isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-    row[k] = make_float4(p.x, p.y, p.z, 0.f);
-  }
-  const bool is_bad = __any(!ok) != 0;
-  if (lane == 0) bad[s] = is_bad ? 1 : 0;
+  const bool ok = gather_structure(xyz + (size_t)s * n * 3, [=](int k) { return sel[k]; }, n, m, packed + (size_t)s * m, lane);
+  if (lane == 0) bad[s] = ok ? 0 : 1;
 }
 
 // grid: x = column tile, y = row tile, z = slice of the structure axis (`per` structures each, a multiple of PD_CHUNK);
@@ -97,8 +89,7 @@ __global__ __launch_bounds__(256) void pairdist_pairs_k(const float4* __restrict
   const int stride = n_bins + 1, cells = (C * (C + 1) / 2) * stride;
   for (int e = tid; e < copies * cells; e += 256) lh[e] = 0u;
   // bit u: the pair (row, cb + u) is this thread's to count -- inside the selection, above the diagonal, not excluded
-  uint32_t ok = 0;
-  if (row < m && cb < m) ok = upper_pair_word(row, cb, m) & ~excl[(size_t)row * words + (cb >> 5)];
+  const uint32_t ok = upper_pair_bits<32>(row, cb, m, excl, words);
   const bool wave_live = __any(ok != 0) != 0;
   int off[32];                                               // where the class pair's row of the histogram starts
   {
@@ -114,14 +105,8 @@ __global__ __launch_bounds__(256) void pairdist_pairs_k(const float4* __restrict
   const int s_begin = (int)blockIdx.z * per, s_end = min(S, s_begin + per);
   for (int s0 = s_begin; s0 < s_end; s0 += PD_CHUNK) {
     __syncthreads();                                         // the previous chunk has been read; the first time: lh is zero
-    if (tid < PD_CHUNK) skip[tid] = s0 + tid < s_end && bad[s0 + tid] == 0 ? 0 : 1;
-    for (int e = tid; e < PD_CHUNK * PD_STAGE; e += 256) {
-      const int sl = e / PD_STAGE, a = e - sl * PD_STAGE;
-      const int at = a < PD_ROWS ? r0 + a : c0 + a - PD_ROWS;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);            // past the slice or the selection: outside every mask
-      if (s0 + sl < s_end && at < m) v = packed[(size_t)(s0 + sl) * m + at];
-      st[sl][a] = v;
-    }
+    // 0 past the slice or the selection: outside every mask
+    stage_chunk<PD_CHUNK, PD_ROWS, PD_COLS>(st, packed, m, r0, c0, s0, s_end, tid, 0.f, bad, skip);
     __syncthreads();
     if (wave_live) {
 #pragma unroll 1
@@ -194,19 +179,18 @@ int cgv_pairdist_counts(const float* xyz, const int32_t* sel, const int32_t* cls
   CGV_REQUIRE(scale > 0.f && scale <= 3.0e38f, "scale must be a finite number > 0");
   if (S == 0) return 0;
   CGV_REQUIRE(xyz && sel && cls && excluded && hist && beyond && bad, "null pointer");
-  CGV_REQUIRE(workspace && workspace_bytes >= cgv::pd_workspace(S, m), "workspace smaller than cgv_pairdist_workspace_bytes()");
-  CGV_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  const char* why = cgv::workspace_why(workspace, workspace_bytes, cgv::pd_workspace(S, m), "workspace smaller than cgv_pairdist_workspace_bytes()");
+  CGV_REQUIRE(why == nullptr, why);
   hipStream_t st = (hipStream_t)stream;
   float4* packed = (float4*)workspace;
   hipLaunchKernelGGL(cgv::pairdist_prep_k, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, xyz, sel, S, n_atoms, m, packed, bad);
   int rc = cgv::check_launch("cgv_pairdist_counts (preparation)");
   if (rc || m < 2) return rc;
-  const int nr = (m + cgv::PD_ROWS - 1) / cgv::PD_ROWS, nc = (m + cgv::PD_COLS - 1) / cgv::PD_COLS;
   int per;
-  const int slices = cgv::struct_slices(S, cgv::upper_live_tiles(nr, nc, cgv::PD_ROWS, cgv::PD_COLS), cgv::PD_CHUNK, &per);
+  const dim3 grid = cgv::pair_grid(S, m, cgv::PD_ROWS, cgv::PD_COLS, cgv::PD_CHUNK, false, &per);
   const int copies = cgv::pd_copies(C, n_bins);
   const size_t lds = (size_t)copies * (size_t)(C * (C + 1) / 2) * (size_t)(n_bins + 1) * sizeof(unsigned int);
-  hipLaunchKernelGGL(cgv::pairdist_pairs_k, dim3((unsigned)nc, (unsigned)nr, (unsigned)slices), dim3(256), lds, st,
+  hipLaunchKernelGGL(cgv::pairdist_pairs_k, grid, dim3(256), lds, st,
                      (const float4*)packed, cls, excluded, (const int*)bad, S, m, (m + 31) / 32, per, C, n_bins, copies, rmax2, scale,
                      (unsigned long long*)hist, (unsigned long long*)beyond);
   return cgv::check_launch("cgv_pairdist_counts");

@@ -40,8 +40,7 @@ import torch
 
 from . import _lib, compare_cli, ensemble
 from .contacts import excluded_pairs
-from .ensemble import device_of, groups_of, read_back, select_atoms, structures
-from .lddt import pack_mask
+from .ensemble import device_of, groups_of, pack_mask, read_back, select_atoms, structures
 
 SCALE = 2.0 ** 20                      # sum_e, sum_e2
 SCALE_DEV = 2.0 ** 12                  # dev2
@@ -58,12 +57,7 @@ def _counted(mask, m: int) -> np.ndarray:
     """``[m, m]`` bool, symmetric, False on the diagonal: the pairs that enter the sums."""
     if mask is None:
         return ~np.eye(m, dtype=bool)
-    a = np.asarray(mask)
-    if a.dtype != np.bool_ or a.shape != (m, m):
-        raise ValueError(f"mask must be a bool array [{m}, {m}], got {a.dtype} {a.shape}")
-    if not np.array_equal(a, a.T):
-        raise ValueError("mask must be symmetric")
-    return ~(a | np.eye(m, dtype=bool))
+    return ~(ensemble.square_mask(mask, m, "mask") | np.eye(m, dtype=bool))
 
 
 def _center(center, counted: np.ndarray) -> Optional[np.ndarray]:

@@ -170,6 +170,27 @@ def check_sets(ref_xyz, gen_xyz, z, *, groups=None, gen_width: bool = True):
     return ref, gen, z
 
 
+# ----------------------------------------------------------------------------- pair masks of the packed pair kernels
+def square_mask(mask, m: int, what: str) -> np.ndarray:
+    """``mask`` as it is when it is a symmetric bool array ``[m, m]``; ``ValueError`` naming ``what`` otherwise."""
+    a = np.asarray(mask)
+    if a.dtype != np.bool_ or a.shape != (m, m):
+        raise ValueError(f"{what} must be a bool array [{m}, {m}], got {a.dtype} {a.shape}")
+    if not np.array_equal(a, a.T):
+        raise ValueError(f"{what} must be symmetric")
+    return a
+
+
+def pack_mask(mask) -> np.ndarray:
+    """``[r, c]`` bool as the pair kernels' ``[r, ceil(c/32)]`` uint32: bit ``j & 31`` of word ``j >> 5``."""
+    a = np.asarray(mask, dtype=bool)
+    r, c = a.shape
+    words = max((c + 31) // 32, 1)
+    padded = np.zeros((r, 32 * words), dtype=bool)
+    padded[:, :c] = a
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4").astype(np.uint32)
+
+
 # ----------------------------------------------------------------------------- topology (host)
 def adjacency(n: int, bonds) -> List[List[int]]:
     b = np.asarray(bonds, dtype=np.int64).reshape(-1, 2)

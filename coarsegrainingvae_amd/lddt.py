@@ -84,17 +84,6 @@ def tolerance_of(tol: float) -> np.float32:
     return t
 
 
-def pack_mask(mask: np.ndarray) -> np.ndarray:
-    """``[m, m]`` bool as the kernel's ``[m, ceil(m/32)]`` uint32: bit ``j & 31`` of word ``j >> 5`` (the layout of
-    ``contacts``)."""
-    m = np.asarray(mask, dtype=bool)
-    r, c = m.shape
-    words = max((c + 31) // 32, 1)
-    padded = np.zeros((r, 32 * words), dtype=bool)
-    padded[:, :c] = m
-    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4").astype(np.uint32)
-
-
 def same_group_pairs(labels) -> np.ndarray:
     """``[m, m]`` bool: True for ``i == j`` and for every pair of atoms with the same label."""
     g = np.asarray(labels).reshape(-1)
@@ -164,7 +153,7 @@ def count_pairs(xyz, ref_xyz, ref_index, sel, excl_lddt, excl_clash, radii, incl
     if S:
         lib = _lib.load()
         d_sel = torch.from_numpy(table).to(dev)
-        d_l, d_c = (torch.from_numpy(pack_mask(e).view(np.int32)).to(dev) for e in (ex_l, ex_c))
+        d_l, d_c = (torch.from_numpy(ensemble.pack_mask(e).view(np.int32)).to(dev) for e in (ex_l, ex_c))
         d_r = torch.from_numpy(r32).to(dev)
         k_most = min(M, S)
         need = int(lib.cgv_lddt_workspace_bytes(k_most, min(k_most, T), m))

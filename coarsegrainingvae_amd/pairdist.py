@@ -39,8 +39,7 @@ import torch
 
 from . import _lib, compare_cli, ensemble
 from .contacts import cutoff2_of, excluded_pairs
-from .ensemble import check_sets, device_of, groups_of, js_divergence, read_back, select_atoms, structures
-from .lddt import pack_mask
+from .ensemble import check_sets, device_of, groups_of, js_divergence, pack_mask, read_back, select_atoms, structures
 
 SYMBOLS = {1: "H", 6: "C", 7: "N", 8: "O", 9: "F", 15: "P", 16: "S", 17: "Cl"}     # names of the element classes; else "Z<z>"
 
@@ -113,12 +112,7 @@ def _labels(classes, z, bonds, mapping):
 
 
 def _square(mask, m: int) -> np.ndarray:
-    a = np.asarray(mask)
-    if a.dtype != np.bool_ or a.shape != (m, m):
-        raise ValueError(f"excluded must be a bool array [{m}, {m}], got {a.dtype} {a.shape}")
-    if not np.array_equal(a, a.T):
-        raise ValueError("excluded must be symmetric")
-    return a | np.eye(m, dtype=bool)
+    return ensemble.square_mask(mask, m, "excluded") | np.eye(m, dtype=bool)
 
 
 # ----------------------------------------------------------------------------- the launches

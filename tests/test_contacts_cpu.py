@@ -3,7 +3,7 @@ statistics on hand-built counts, the command-line switches and the C ABI's decla
 import numpy as np
 import pytest
 
-from coarsegrainingvae_amd import _lib, backmap as bm, contacts, run_ala
+from coarsegrainingvae_amd import _lib, backmap as bm, contacts, ensemble, run_ala
 import contacts_restatement as R
 import internal_coords_restatement as IR
 
@@ -76,8 +76,8 @@ def test_excluded_pairs_on_a_chain_a_ring_and_two_molecules():
 def test_the_bit_masks_are_words_of_32_pairs():
     mask = np.zeros((3, 40), dtype=bool)
     mask[0, 31] = mask[1, 33] = mask[2, 0] = mask[2, 39] = True
-    assert contacts._pack_bits(mask).tolist() == [[1 << 31, 0], [0, 2], [1, 1 << 7]]
-    assert contacts._pack_bits(mask).dtype == np.uint32 and contacts._pack_bits(np.zeros((2, 64), dtype=bool)).shape == (2, 2)
+    assert ensemble.pack_mask(mask).tolist() == [[1 << 31, 0], [0, 2], [1, 1 << 7]]
+    assert ensemble.pack_mask(mask).dtype == np.uint32 and ensemble.pack_mask(np.zeros((2, 64), dtype=bool)).shape == (2, 2)
     assert float(contacts.cutoff2_of(3.0)) == 9.0 and contacts.cutoff2_of(4.5).dtype == np.float32
     assert contacts.cutoff2_of(0.1) == np.float32(np.float32(0.1) * np.float32(0.1))
     with pytest.raises(ValueError):

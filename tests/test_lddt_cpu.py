@@ -6,7 +6,7 @@ import json
 import numpy as np
 import pytest
 
-from coarsegrainingvae_amd import _lib, build, contacts, lddt
+from coarsegrainingvae_amd import _lib, build, contacts, ensemble, lddt
 import density_restatement as DR
 import lddt_restatement as R
 
@@ -91,12 +91,12 @@ def test_the_masks_of_both_kinds():
     assert same.diagonal().all() and np.array_equal(same, same.T) and same.sum() == sum(int((labels == g).sum()) ** 2 for g in range(3))
     by_bonds = contacts.excluded_pairs(bonds, n, np.arange(n), 2)
     assert by_bonds[0, 3] and not by_bonds[0, 4] and by_bonds.diagonal().all()  # CH3 - C - N is two bonds, CA three
-    packed = lddt.pack_mask(by_bonds)
-    assert packed.dtype == np.uint32 and packed.shape == (n, 1) and np.array_equal(packed, contacts._pack_bits(by_bonds))
+    packed = ensemble.pack_mask(by_bonds)
+    assert packed.dtype == np.uint32 and packed.shape == (n, 1)
+    assert packed.tolist() == [[sum(1 << int(j) for j in np.flatnonzero(row))] for row in by_bonds]     # n <= 32: one word a row
     wide = np.zeros((3, 65), dtype=bool)
     wide[0, 0] = wide[1, 31] = wide[1, 32] = wide[2, 64] = True
-    assert lddt.pack_mask(wide).tolist() == [[1, 0, 0], [1 << 31, 1, 0], [0, 0, 1]]
-    assert np.array_equal(lddt.pack_mask(wide), contacts._pack_bits(wide))
+    assert ensemble.pack_mask(wide).tolist() == [[1, 0, 0], [1 << 31, 1, 0], [0, 0, 1]]
 
 
 def test_the_ref_index_defaults_and_the_refusal():

@@ -31,7 +31,7 @@ CUTOFF = 4.5
 def main():
     import numpy as np
     import torch
-    from coarsegrainingvae_amd import _lib, contacts
+    from coarsegrainingvae_amd import _lib, contacts, ensemble
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", type=str, default=None)
@@ -64,7 +64,7 @@ def main():
         sel = np.sort(rng.permutation(n)[:m])
         excl = contacts.excluded_pairs(np.stack([np.arange(n - 1), np.arange(1, n)], 1), n, sel, 3)
         d_sel = torch.from_numpy(sel.astype(np.int32)).to(dev)
-        d_excl = torch.from_numpy(contacts._pack_bits(excl).view(np.int32)).to(dev)
+        d_excl = torch.from_numpy(ensemble.pack_mask(excl).view(np.int32)).to(dev)
         allowed = torch.from_numpy(~excl).to(dev)
         counts = torch.zeros(m, m, dtype=torch.int32, device=dev)
         per = [torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(3)]

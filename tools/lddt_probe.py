@@ -32,7 +32,7 @@ R0, THRESHOLDS, TOL, RADIUS = 15.0, (0.5, 1.0, 2.0, 4.0), 0.4, 1.7
 def main():
     import numpy as np
     import torch
-    from coarsegrainingvae_amd import _lib, lddt
+    from coarsegrainingvae_amd import _lib, ensemble, lddt
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", type=str, default=None)
@@ -65,7 +65,7 @@ def main():
         band = np.zeros((m, m), dtype=bool)
         for k in range(-3, 4):
             band |= np.eye(m, k=k, dtype=bool)
-        d_excl = torch.from_numpy(lddt.pack_mask(band).view(np.int32)).to(dev)
+        d_excl = torch.from_numpy(ensemble.pack_mask(band).view(np.int32)).to(dev)
         allowed = torch.from_numpy(~band).to(dev)
         d_sel = torch.arange(m, dtype=torch.int32, device=dev)
         d_r = torch.full((m,), RADIUS, dtype=torch.float32, device=dev)

@@ -39,7 +39,7 @@ def k20_rate():
 def main():
     import numpy as np
     import torch
-    from coarsegrainingvae_amd import _lib, pairdist
+    from coarsegrainingvae_amd import _lib, ensemble, pairdist
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", type=str, default=None)
@@ -75,7 +75,7 @@ def main():
         x = torch.from_numpy(np.cumsum(step, axis=1).astype(np.float32)).to(dev)
         i = np.arange(m)
         band = np.abs(i[:, None] - i[None, :]) <= 3
-        d_excl = torch.from_numpy(pairdist.pack_mask(band).view(np.int32)).to(dev)
+        d_excl = torch.from_numpy(ensemble.pack_mask(band).view(np.int32)).to(dev)
         counted = torch.from_numpy(np.triu(~band, 1)).to(dev)
         d_sel = torch.arange(m, dtype=torch.int32, device=dev)
         need = int(lib.cgv_pairdist_workspace_bytes(S, m))
