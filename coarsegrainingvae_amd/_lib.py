@@ -277,6 +277,19 @@ PROTOTYPES = {
     "cgv_dist_moments_chunk": (_i, []),
     "cgv_dist_moments_workspace_bytes": (_sz, [_i, _i]),
     "cgv_dist_moments": (_i, [_p] * 4 + [_i] * 3 + [_p] * 4 + [_p, _sz, _p]),
+    "cgv_stereo_max_structures": (_i, []),
+    "cgv_stereo_max_atoms": (_i, []),
+    "cgv_stereo_max_centres": (_i, []),
+    "cgv_stereo_max_torsions": (_i, []),
+    "cgv_stereo_max_rings": (_i, []),
+    "cgv_stereo_max_bonds": (_i, []),
+    "cgv_stereo_max_ring": (_i, []),
+    "cgv_stereo_item_tile": (_i, []),
+    "cgv_stereo_row_tile": (_i, []),
+    "cgv_stereo_col_tile": (_i, []),
+    "cgv_stereo_chunk": (_i, []),
+    "cgv_stereo_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cgv_stereo_counts": (_i, [_p] * 9 + [_i] * 7 + [_p] * 6 + [_p, _sz, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

@@ -14,6 +14,8 @@
 //   K28 lddt.hip          all but stage_chunk (it stages a model and its reference in one loop) and upper_pair_bits (ordered pairs)
 //   K29 pair_hist.hip     all but ChunkCounts (its counters are the histogram)
 //   K30 dist_moments.hip  x
+//   K31 stereo.hip        gather_structure, poison_row, ChunkCounts, struct_slices, workspace_why (its tables are quadruples and a
+//                         rectangle of rings against bonds, not pairs of one selection; it does not include sq_dist.h's distance)
 #pragma once
 #include <math.h>
 

@@ -1683,6 +1683,70 @@ int cgv_dist_moments(const float* xyz, const int32_t* sel /*[m]*/, const uint32_
                      int64_t* sum_e2 /*[m,m]*/, int64_t* dev2 /*[S]*/, int32_t* bad /*[S]*/, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K31  stereochemistry of an ensemble -- over the structures of a call, how often every stereocentre is of the negative hand
+ * or flat, how often every torsion about a bond that does not rotate is cis, how often every bond pierces every ring, and
+ * per structure the centres of the wrong hand, the torsions in the wrong state and the pierced (ring, bond) pairs.  Nothing
+ * in the reference computes it.
+ *   xyz [n_structures,n_atoms,3] fp32         the structures
+ *   sel [P] int32                             the atoms that the tables name.  An index outside [0, n_atoms) reads atom 0.
+ *   centres [C,4], torsions [Q,4] int32       (c, a, b, d) and (i, j, k, l): PLACES in sel
+ *   rings [R, cgv_stereo_max_ring()] int32    places in sel along the cycle, 3 to 8 of them, then -1; a row with fewer than
+ *                                             3 is pierced by nothing
+ *   bonds [B,2] int32                         places in sel
+ *                                             A place outside [0, P) reads place 0 (the host wrapper refuses such tables);
+ *                                             nothing is read out of bounds.
+ *   tested [R,W] uint32, W = ceil(B / 32)     bit (b & 31) of word b >> 5 of row r: the pair (ring r, bond b) is looked at;
+ *                                             bits past B are ignored
+ *   want_sign [C] int32 (-1 / +1), want_cis [Q] int32 (0 / 1)      or NULL: that counter of `counts` stays 0
+ * In fp32 with every operation individually rounded (no fma, no square root, no division), with
+ *   x(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x)      d(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z
+ *   centre   V = d(a - c, x(b - c, d - c))                     negative: V < 0      flat: V == 0
+ *   torsion  X = d(x(j - i, k - j), x(k - j, l - k))           cis: X > 0
+ *   ring v_0 .. v_{k-1} against the bond (p0, p1):   g = (((v_0 + v_1) + v_2) + ...) * fp32(1 / k),  dir = p1 - p0,  tvec = p0 - g;
+ *     for every triangle (g, v_t, v_{t+1 mod k}) of the fan:  e1 = v_t - g, e2 = v_{t+1} - g,
+ *       pv = x(dir, e2)   det = d(e1, pv)   u' = d(tvec, pv)   q = x(tvec, e1)   v' = d(dir, q)   t' = d(e2, q)   w' = u' + v'
+ *       crossed:  det > 0 and u' >= 0 and v' >= 0 and w' <= det and t' >= 0 and t' <= det
+ *             or  det < 0 and u' <= 0 and v' <= 0 and w' >= det and t' <= 0 and t' >= det         (det == 0: not crossed)
+ *     pierced: at least one triangle is crossed.  There is no pre-filter: every tested pair gets the full fan.
+ * A host that restates the arithmetic gets every integer below exactly; no floating-point result leaves the device.
+ *   neg, flat [C] int64, cis [Q] int64        ADDED to: the good structures in which the centre is negative / flat, the
+ *                                             torsion cis.  The caller zeroes them once and may cut an ensemble into launches.
+ *   pierced [R,B] int32                       ADDED to, and only where a tested pair is pierced
+ *   counts [n_structures,3] int32             overwritten: centres whose sign (-1, 0 for flat, +1) differs from want_sign,
+ *                                             torsions whose state differs from want_cis, pierced tested pairs; 0 for a bad
+ *                                             structure
+ *   bad [n_structures] int32                  overwritten: 1 for a structure with a non-finite coordinate among the atoms of
+ *                                             sel; it enters nothing.  Atoms outside sel are not looked at.
+ * Launches: one wave per structure gathers sel, and the R ring centres, into a packed float4 copy in the workspace; a light
+ *   pass with a lane per centre or torsion (tiles of cgv_stereo_item_tile()); then grid (tiles of cgv_stereo_col_tile()
+ *   bonds, tiles of cgv_stereo_row_tile() rings, slices of the structure axis) x 256 threads with cgv_stereo_chunk()
+ *   structures at a time in LDS.  Integer sums meet in atomicAdd: the same bits on every call, however the structures are cut.
+ *   C, Q, R, B may each be 0; with all four 0 only bad (and counts = 0) is written.
+ * workspace: cgv_stereo_workspace_bytes(n_structures, P, R) bytes (0 beyond a limit), 16-byte aligned, contents need not
+ *   survive.
+ * Limits: cgv_stereo_max_structures() per launch, P <= cgv_stereo_max_atoms() and <= n_atoms, cgv_stereo_max_centres(),
+ *   _torsions(), _rings(), _bonds().  Beyond a limit the call fails (CGV_E_BADARG) with its reason before any launch and
+ *   writes nothing; n_structures = 0 returns 0 and does nothing.  See DESIGN.md (ST row). */
+int cgv_stereo_max_structures(void);
+int cgv_stereo_max_atoms(void);
+int cgv_stereo_max_centres(void);
+int cgv_stereo_max_torsions(void);
+int cgv_stereo_max_rings(void);
+int cgv_stereo_max_bonds(void);
+int cgv_stereo_max_ring(void);
+int cgv_stereo_item_tile(void);
+int cgv_stereo_row_tile(void);
+int cgv_stereo_col_tile(void);
+int cgv_stereo_chunk(void);
+size_t cgv_stereo_workspace_bytes(int n_structures, int n_sel, int n_rings);
+int cgv_stereo_counts(const float* xyz, const int32_t* sel /*[P]*/, const int32_t* centres /*[C,4]*/, const int32_t* torsions /*[Q,4]*/,
+                      const int32_t* rings /*[R,8]*/, const int32_t* bonds /*[B,2]*/, const uint32_t* tested /*[R,W]*/,
+                      const int32_t* want_sign /*[C] or NULL*/, const int32_t* want_cis /*[Q] or NULL*/, int n_structures,
+                      int n_atoms, int n_sel, int n_centres, int n_torsions, int n_rings, int n_bonds, int64_t* neg /*[C]*/,
+                      int64_t* flat /*[C]*/, int64_t* cis /*[Q]*/, int32_t* pierced /*[R,B]*/, int32_t* counts /*[S,3]*/,
+                      int32_t* bad /*[S]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
