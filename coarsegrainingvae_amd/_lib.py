@@ -290,6 +290,11 @@ PROTOTYPES = {
     "cgv_stereo_chunk": (_i, []),
     "cgv_stereo_workspace_bytes": (_sz, [_i, _i, _i]),
     "cgv_stereo_counts": (_i, [_p] * 9 + [_i] * 7 + [_p] * 6 + [_p, _sz, _p]),
+    "cgv_relax_max_atoms": (_i, []),
+    "cgv_relax_max_structures": (_i, []),
+    "cgv_relax_max_steps": (_i, []),
+    "cgv_relax_pack": (_i, [_i]),
+    "cgv_relax": (_i, [_p] * 9 + [_i] * 3 + [_f] * 5 + [_i] + [_p] * 5 + [_p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

@@ -16,6 +16,10 @@
 //   K30 dist_moments.hip  x
 //   K31 stereo.hip        gather_structure, poison_row, ChunkCounts, struct_slices, workspace_why (its tables are quadruples and a
 //                         rectangle of rings against bonds, not pairs of one selection; it does not include sq_dist.h's distance)
+//   K32 relax.hip         word_inside alone, with sq_dist.h's sq_dist2 and sq_wave_sum.  It streams no packed copy: a structure
+//                         is loaded once into LDS and stays there for all steps, every atom against every atom, so there is no
+//                         workspace (workspace_why), no tile or slice (struct_slices, pair_grid, stage_chunk, upper_*), no
+//                         selection (gather_structure), and its per-structure results are written once, not counted (ChunkCounts)
 #pragma once
 #include <math.h>
 

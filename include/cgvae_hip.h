@@ -1747,6 +1747,52 @@ int cgv_stereo_counts(const float* xyz, const int32_t* sel /*[P]*/, const int32_
                       int64_t* flat /*[C]*/, int64_t* cis /*[Q]*/, int32_t* pierced /*[R,B]*/, int32_t* counts /*[S,3]*/,
                       int32_t* bad /*[S]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K32  restrained geometry relaxation of an ensemble -- `steps` damped Jacobi steps of every structure towards the restraint
+ * table's distances and out of its steric clashes (K28's predicate), a weak spring holding every atom at its anchor.  The
+ * one entry point that returns coordinates.  Nothing in the reference computes it.
+ *   xyz, anchor [n_structures,n_atoms,3] fp32   the structures and where their atoms are held (may be the same pointer)
+ *   row_ptr [n_atoms+1], partner, d0, w [E]     the restraints in per-atom CSR form: every restraint {i, j} under both atoms,
+ *                                               an atom's entries in the order of the host table.  A partner outside
+ *                                               [0, n_atoms) reads atom 0 and a row_ptr outside [0, E] is clamped (the host
+ *                                               wrapper refuses such tables); nothing is read out of bounds.
+ *   wsum [n_atoms] fp32                         W_i: the fp32 sum of the atom's w in table order, made on the host
+ *   radii [n_atoms] fp32, excl [n_atoms,W] uint32, W = ceil(n_atoms / 32)      bit (j & 31) of word j >> 5 of row i: the pair is
+ *                                               no clash whatever its distance (ensemble.pack_mask)
+ * In fp32 with every operation individually rounded (sqrtf and / correctly rounded), for atom i from the positions of the
+ * PREVIOUS step (two buffers, a barrier between steps: nothing depends on which thread owns which atom):
+ *   g = k_pos * (x_i - a_i)
+ *   restraints in table order:   D = x_i - x_j, q = (D.x*D.x + D.y*D.y) + D.z*D.z; if q > 0: d = sqrtf(q), g = g + ((w * (d - d0)) / d) * D
+ *   j ascending, j != i, not excl:   c = (r_i + r_j) - tol; if c > 0 and q < c * c and q > 0: g = g + ((k_rep * (d - c)) / d) * D, nc += 1
+ *   h = (k_pos + 2 * W_i) + (2 * k_rep) * float(nc)
+ *   h > 0:  delta = (-(damp / h)) * g;  m = (delta.x^2 + delta.y^2) + delta.z^2;  if m > cap * cap: delta = delta * (cap / sqrtf(m))
+ *   x_i' = x_i + delta                                                          (h > 0 fails: delta = 0)
+ * A host that restates the arithmetic gets xyz_out, clashes, disp2 and bad bit for bit.
+ *   xyz_out [n_structures,n_atoms,3] fp32       overwritten; must not overlap xyz or anchor
+ *   clashes [n_structures,2] int32              the pairs i < j with c > 0 and q < c * c before the first step and after the last
+ *   energy [n_structures,2] fp64                before and after: per atom, in fp64 from the fp32 distances,
+ *                                               (0.5 k_pos) |x - a|^2, (0.25 w)(d - d0)^2 per entry, (0.25 k_rep)(d - c)^2 per
+ *                                               clashing partner, summed in a fixed tree (no floating-point atomics): the same
+ *                                               bits on every call, within N_terms * 2^-53 relative of the exact sum
+ *   disp2 [n_structures] fp32                   the largest squared displacement from the anchor after the last step
+ *   bad [n_structures] int32                    1 for a structure with a non-finite coordinate or anchor: its coordinates are
+ *                                               copied through and its other outputs are 0
+ * steps = 0 copies the input and reports the same before and after.
+ * Launch: 256 threads; cgv_relax_pack(n_atoms) structures share a block (4 for up to 64 atoms, 2 for up to 128, else 1), each
+ *   resident in LDS (44 bytes an atom) for all steps; a thread owns the atoms t, t + T, ...
+ * Limits: cgv_relax_max_structures() per launch, n_atoms <= cgv_relax_max_atoms() (what fits a CU's 160 KB of LDS),
+ *   steps <= cgv_relax_max_steps(); k_pos, k_rep, tol, damp finite and >= 0, cap finite and > 0.  Beyond a limit the call fails
+ *   (CGV_E_BADARG) with its reason before any launch and writes nothing; n_structures = 0 returns 0 and does nothing. */
+int cgv_relax_max_atoms(void);
+int cgv_relax_max_structures(void);
+int cgv_relax_max_steps(void);
+int cgv_relax_pack(int n_atoms);
+int cgv_relax(const float* xyz, const float* anchor, const int32_t* row_ptr /*[n+1]*/, const int32_t* partner /*[E]*/,
+              const float* d0 /*[E]*/, const float* w /*[E]*/, const float* wsum /*[n]*/, const float* radii /*[n]*/,
+              const uint32_t* excl /*[n,W]*/, int n_structures, int n_atoms, int n_entries, float k_pos, float k_rep, float tol,
+              float damp, float cap, int steps, float* xyz_out, int32_t* clashes /*[S,2]*/, double* energy /*[S,2]*/,
+              float* disp2 /*[S]*/, int32_t* bad /*[S]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
