@@ -295,6 +295,17 @@ PROTOTYPES = {
     "cgv_relax_max_steps": (_i, []),
     "cgv_relax_pack": (_i, [_i]),
     "cgv_relax": (_i, [_p] * 9 + [_i] * 3 + [_f] * 5 + [_i] + [_p] * 5 + [_p]),
+    "cgv_saxs_max_atoms": (_i, []),
+    "cgv_saxs_max_structures": (_i, []),
+    "cgv_saxs_max_bins": (_i, []),
+    "cgv_saxs_max_weight": (_i, []),
+    "cgv_saxs_row_tile": (_i, []),
+    "cgv_saxs_col_tile": (_i, []),
+    "cgv_saxs_small": (_i, []),
+    "cgv_saxs_pack": (_i, [_i, _i]),
+    "cgv_saxs_blocks": (_i, [_i, _i, _i]),
+    "cgv_saxs_workspace_bytes": (_sz, [_i, _i]),
+    "cgv_saxs_hist": (_i, [_p] * 3 + [_i] * 4 + [_f] * 2 + [_i] + [_p] * 3 + [_p, _sz, _p]),
     "cgv_align_max_atoms": (_i, []),
     "cgv_align_max_structures": (_i, []),
     "cgv_align_wave_fits": (_i, [_i]),

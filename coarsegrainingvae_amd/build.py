@@ -41,7 +41,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contract=
 # same way; the stereochemistry kernel reads the SIGN of a rounded triple product, of a rounded dot product of two rounded
 # cross products, and of the rounded numerators of a segment-triangle intersection against each other, restated the same way;
 # the relaxation kernel's whole step -- rounded products, quotients and square roots of sq_dist2, 25 steps deep -- is restated
-# in numpy.float32 and its coordinates compared bit for bit.
+# in numpy.float32 and its coordinates compared bit for bit; the scattering kernel bins by K29's rule, restated the same way.
 # kde.hip has NO entry: its fp32 stage sums are checked against an error bound, not restated bit for bit, and its one
 # contraction that matters (the minimum image) is written as an explicit fmaf -- the default flags do; cluster.hip has none
 # either: its only floating-point operation is a comparison of doubles that K17 wrote
@@ -52,7 +52,8 @@ SOURCE_FLAGS = {"newman.hip": ["-ffp-contract=off"], "baseline.hip": ["-ffp-cont
                 "sasa.hip": ["-ffp-contract=off"], "hbond.hip": ["-ffp-contract=off"],
                 "dssp.hip": ["-ffp-contract=off"], "pca.hip": ["-ffp-contract=off"], "lddt.hip": ["-ffp-contract=off"],
                 "pair_hist.hip": ["-ffp-contract=off"], "dist_moments.hip": ["-ffp-contract=off"],
-                "stereo.hip": ["-ffp-contract=off"], "relax.hip": ["-ffp-contract=off"]}
+                "stereo.hip": ["-ffp-contract=off"], "relax.hip": ["-ffp-contract=off"],
+                "saxs_hist.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -1,5 +1,5 @@
 """The front end of the stand-alone command lines that compare generated structures with a reference (``sasa``,
-``cluster``, ``hbonds``, ``dssp``, ``pca``, ``lddt``, ``pairdist``, ``distmat``, ``stereo``, ``relax``): the options and files they all take, the refusals that need no device, and the way they end.  Pure
+``cluster``, ``hbonds``, ``dssp``, ``pca``, ``lddt``, ``pairdist``, ``distmat``, ``stereo``, ``relax``, ``saxs``): the options and files they all take, the refusals that need no device, and the way they end.  Pure
 host code: it launches no kernel and imports none of the analyses; they import it, and add their own options and checks
 between ``base_parser`` and ``finish_parser``, and after ``read_sets``.
 """

@@ -20,6 +20,10 @@
 //                         is loaded once into LDS and stays there for all steps, every atom against every atom, so there is no
 //                         workspace (workspace_why), no tile or slice (struct_slices, pair_grid, stage_chunk, upper_*), no
 //                         selection (gather_structure), and its per-structure results are written once, not counted (ChunkCounts)
+//   K33 saxs_hist.hip     gather_structure, upper_tile_live, upper_pair_bits, workspace_why.  Its histograms are one per
+//                         structure, so a block stays with ONE structure and the structure axis is not cut (struct_slices,
+//                         pair_grid) or staged in chunks (stage_chunk: its staged float4 carries the atom's weight in w), and
+//                         its counters are the histogram (ChunkCounts)
 #pragma once
 #include <math.h>
 

@@ -13,6 +13,7 @@
 //   K30 dist_moments.hip                             sqrtf(sq_dist2) minus a centre and its square, rounded to fixed point; the wave sum
 //   K31 stereo.hip (through packed_dev.h)            not the distance: the signs of rounded cross and dot products, restated the same way
 //   K32 relax.hip (through packed_dev.h)             sq_dist2 as the q of every force and of K28's clash test; the wave sums of its energy
+//   K33 saxs_hist.hip                                K29's bin of sqrtf(sq_dist2) and sq_dist2 < rmax2, per structure and weighted
 // packed_dev.h and gram_dev.h stand on the same contract.
 #pragma once
 #include "cgv_common.h"

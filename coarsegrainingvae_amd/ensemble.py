@@ -1,7 +1,7 @@
 """What the analyses of ensembles share (``evaluate``, ``distributions``, ``tica``, ``coverage``, ``contacts``,
-``flexibility``, ``density``, ``sasa``, ``cluster``, ``hbonds``, ``dssp``, ``pca``, ``lddt``, ``pairdist``, ``distmat``, ``stereo``, ``relax``): the host plumbing around their kernels and the topology helpers more
+``flexibility``, ``density``, ``sasa``, ``cluster``, ``hbonds``, ``dssp``, ``pca``, ``lddt``, ``pairdist``, ``distmat``, ``stereo``, ``relax``, ``saxs``): the host plumbing around their kernels and the topology helpers more
 than one of them reads.  This module imports none of them, so each imports it at module level; what is here is public, and nothing here
-launches a kernel.  The front end of the stand-alone command lines (``sasa``, ``cluster``, ``hbonds``, ``dssp``, ``pca``, ``lddt``, ``pairdist``, ``distmat``, ``stereo``, ``relax``: files, parser, summary line) is
+launches a kernel.  The front end of the stand-alone command lines (``sasa``, ``cluster``, ``hbonds``, ``dssp``, ``pca``, ``lddt``, ``pairdist``, ``distmat``, ``stereo``, ``relax``, ``saxs``: files, parser, summary line) is
 ``compare_cli``, which imports this module and is imported by them.
 """
 from __future__ import annotations

@@ -1793,6 +1793,49 @@ int cgv_relax(const float* xyz, const float* anchor, const int32_t* row_ptr /*[n
               float damp, float cap, int steps, float* xyz_out, int32_t* clashes /*[S,2]*/, double* energy /*[S,2]*/,
               float* disp2 /*[S]*/, int32_t* bad /*[S]*/, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * K33  weighted pair-distance histograms of an ensemble, one per structure: what the small-angle scattering profile I(q),
+ * the weighted P(r), Rg and Dmax of every structure are made from on the host (saxs.py).  Nothing in the reference computes
+ * it.
+ *   xyz [n_structures,n_atoms,3] fp32, sel [m]  the structures and the selected atoms (an index outside [0, n_atoms) reads
+ *                                               atom 0; the host wrapper refuses such a table)
+ *   wq [m] int32                                the fixed-point weight of every selected atom, |wq| <= cgv_saxs_max_weight()
+ *                                               (the host's rint(w * 16); the kernel multiplies whatever it is given in 32 bits)
+ * For a good structure s and EVERY pair i < j of the selection (no exclusion mask), in fp32 with every operation
+ * individually rounded (sqrtf correctly rounded) -- K29's bin rule:
+ *   q = (dx*dx + dy*dy) + dz*dz;  in range iff q < rmax2 (strict);  b = min((int)(sqrtf(q) * scale), n_bins - 1)
+ *   in range:  hist[s][b] += wq_i * wq_j          otherwise:  beyond[s] += 1   (a count of pairs, whatever their weights)
+ *   hist [n_structures,n_bins] int64, beyond [n_structures] int64      ADDED to: the caller zeroes them; integer atomics only
+ *   bad [n_structures] int32                    overwritten: 1 for a structure with a non-finite selected coordinate, which
+ *                                               adds nothing to its rows
+ * A host that restates the arithmetic gets every integer; no floating-point number leaves the device; the same bits on
+ * every call, however the structures are cut into launches and however many blocks share a structure.
+ *   split                                       0: the library decides how many blocks share a structure of more than
+ *                                               cgv_saxs_small() atoms (cgv_saxs_blocks); > 0: that many, at most one per
+ *                                               row tile -- for tests and measurements, the result does not depend on it
+ * Launch: a preparation launch (one wave per structure) packs the selection into the workspace; then, for m <=
+ *   cgv_saxs_small(), cgv_saxs_pack(m, n_bins) structures share a block, a wave each; else cgv_saxs_blocks() blocks of 256
+ *   threads share a structure, each walking its row tiles (cgv_saxs_row_tile() x cgv_saxs_col_tile()) above the diagonal.
+ *   The block's histogram is private in LDS, n_bins signed 64-bit cells.
+ * Overflow: |wq_i wq_j| < 2^30, fewer than 2^25 pairs per structure: |hist[s][b]| < 2^55.
+ * Limits: cgv_saxs_max_structures() per launch, m <= cgv_saxs_max_atoms(), n_bins <= cgv_saxs_max_bins(); rmax2 finite and
+ *   >= 0, scale finite and > 0.  Beyond a limit the call fails (CGV_E_BADARG) with its reason before any launch and writes
+ *   nothing; n_structures = 0 returns 0 and does nothing.  workspace: cgv_saxs_workspace_bytes() bytes (0 for sizes beyond
+ *   the limits), 16-byte aligned. */
+int cgv_saxs_max_atoms(void);
+int cgv_saxs_max_structures(void);
+int cgv_saxs_max_bins(void);
+int cgv_saxs_max_weight(void);
+int cgv_saxs_row_tile(void);
+int cgv_saxs_col_tile(void);
+int cgv_saxs_small(void);
+int cgv_saxs_pack(int m, int n_bins);
+int cgv_saxs_blocks(int n_structures, int m, int split);
+size_t cgv_saxs_workspace_bytes(int n_structures, int m);
+int cgv_saxs_hist(const float* xyz, const int32_t* sel /*[m]*/, const int32_t* wq /*[m]*/, int n_structures, int n_atoms, int m,
+                  int n_bins, float rmax2, float scale, int split, int64_t* hist /*[S,n_bins]*/, int64_t* beyond /*[S]*/,
+                  int32_t* bad /*[S]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
